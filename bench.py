@@ -10,6 +10,9 @@ N > 1 -- the single all-gather of the (256, 1000) logits that data-parallel infe
 (SURVEY.md 8e).  Inputs are already in HBM when the timed region starts.  Protocol of the
 reference's compare.py:149-158: warm-up, device sync, K timed forwards, device sync.
 
+With --dump-outputs DIR, rank 0 also writes the logits the last timed step returned as DIR/logits.npy (float32; inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output).
+
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline     -- the dominant kernel (channel-MLP GEMM, 79 % of the flops): algorithmic
                   2*M*N*K per launch / HIP-event time of those launches inside the timed region,
@@ -22,9 +25,11 @@ import argparse
 import importlib
 import json
 import os
+import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -195,6 +200,21 @@ def measured_traffic(args):
     return t.get("channel_mlp_gemm_bytes_per_launch"), "%s (git %s)" % (os.path.basename(files[-1]), t.get("git", "?"))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_output(dirname, name, t):
+    """--dump-outputs: what the timed path returned in its last step, as DIR/<name>.npy in float32, so that two builds can be compared
+    output for output on the same seeded inputs.  Above 64 MB, a fixed sample of the rows is kept (seeded, in ascending order: the same
+    rows on every run with the same arguments)."""
+    os.makedirs(dirname, exist_ok=True)
+    a = t.detach().float().cpu().numpy()
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // max(1, a[:1].nbytes))
+        a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def cpu_stub(args, world, rank):
     """The N-rank protocol of this file without a GPU: gloo, every rank "computes" deterministic logits for its shard, the
     single all-gather, barrier-bracketed timing with the max over ranks, one JSON line from rank 0."""
@@ -226,6 +246,8 @@ def cpu_stub(args, world, rank):
     # shard r of the gathered logits carries + r: the gather kept the rank order
     assert all(abs(float(out[r * args.batch, 0] - out[0, 0]) - r) < 1e-6 for r in range(world))
     if rank == 0:
+        if args.dump_outputs:
+            dump_output(args.dump_outputs, "logits", out)
         print(json.dumps({"metric": "images/sec fwd (cpu stub)", "value": round(args.batch * world * args.steps / elapsed, 1), "unit": "images/s",
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "fp32", "data": "synthetic",
@@ -260,7 +282,11 @@ def main():
     ap.add_argument("--share-device", action="store_true", help="testing only: every rank uses cuda:0")
     ap.add_argument("--cpu-stub", action="store_true", help="testing only (tests/test_parallel_gloo.py): no GPU, gloo, a stub forward "
                     "-- exercises the launcher, the barrier / max-over-ranks timing and the logits gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the logits the last timed step returned (all ranks, gathered) as DIR/logits.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -274,7 +300,7 @@ def main():
                    os.path.abspath(__file__)] + sys.argv[1:]
             os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
             sys.stdout.flush()
-            os.execv(sys.executable, cmd)
+            raise SystemExit(subprocess.call(cmd))      # a child process, not exec: this process may already hold a HIP runtime
         raise SystemExit("--gpus %d does not match WORLD_SIZE %d" % (args.gpus, world))
     if args.cpu_stub:
         return cpu_stub(args, world, rank)
@@ -394,6 +420,7 @@ def main():
             dist.barrier()
         t1 = time.perf_counter()
         sensors = sampler.stop() if sampler is not None else None
+        last_out = out.float().cpu() if args.dump_outputs and rank == 0 else None       # the last timed step's logits, before any later pass
         timer_after = None
         if side is None:
             timer, timing_steps = kernel_timing_pass()
@@ -495,6 +522,8 @@ def main():
                 line["cpu_baseline"] = run_cpu_baseline(args.model, kwargs, ctor_name, pkg)
             except Exception as e:      # a baseline failure must not discard the measured GPU line
                 line["cpu_baseline"] = {"value": None, "unit": "images/s", "cores": 0, "kind": "port", "sample": "failed: %r" % (e,)}
+        if last_out is not None:
+            dump_output(args.dump_outputs, "logits", last_out)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -94,3 +94,34 @@ def test_bench_launches_itself_for_n_ranks():
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "4", "--cpu-stub"],
                         capture_output=True, text=True, timeout=300, env=env)
     assert r1.returncode == 0 and json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
+
+
+def test_bench_dumps_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR` writes the logits the last timed step returned (gathered over the ranks) as DIR/logits.npy in float32;
+    `--steps` below 1 is refused rather than timing nothing."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--cpu-stub",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    a = np.load(out / "logits.npy")
+    assert a.dtype == np.float32 and a.shape == (8, 1000)
+    assert np.array_equal(a[4:], a[:4] + 1.0)                 # the stub's rank-1 shard, gathered behind rank 0's
+    r0 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--cpu-stub"], capture_output=True, text=True, timeout=300, env=env)
+    assert r0.returncode != 0 and "--steps" in r0.stderr
+
+
+def test_bench_dump_keeps_a_fixed_sample_of_a_large_output(tmp_path, monkeypatch):
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 1000 * 4)
+    x = torch.arange(1000, dtype=torch.float32)[:, None].repeat(1, 1000)          # row i holds i
+    bench.dump_output(str(tmp_path / "a"), "logits", x)
+    bench.dump_output(str(tmp_path / "b"), "logits", x)
+    a, b = np.load(tmp_path / "a" / "logits.npy"), np.load(tmp_path / "b" / "logits.npy")
+    assert a.dtype == np.float32 and a.shape == (64, 1000) and a.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(a, b)                                # the same rows on every run
+    assert (a == a[:, :1]).all() and (np.diff(a[:, 0]) > 0).all()     # whole rows of the output, distinct, in order
