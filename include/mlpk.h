@@ -723,6 +723,15 @@ int mlpk_s2_shift2(int dtype, int which, int mode, int adjoint, const void* in, 
  * 104-131: CycleFC's fixed integer offsets, width = 1); the table of the inverse relation (kmax = largest multiplicity) is the adjoint -- the gradient. */
 int mlpk_index_gather(int dtype, const void* src, void* dst, const int* idx, int batch, int64_t n_out, int64_t n_in, int width, int kmax, void* stream);
 
+/* nn.Dropout in train mode (the rate of SwinMLP / AS_MLP / MS_MLP's drop_rate): pos_drop after the embedding (swin_mlp.py:390,437-439;
+ * as_mlp.py:391,430; ms_mlp.py:314,354) and Mlp.drop after the hidden GELU and after fc2 (swin_mlp.py:23-30,108,155; as_mlp.py:16-23,147,160).
+ * x, y: a logical row-major (rows, cols) tensor with row pitches ldx / ldy; x == y (with ldx == ldy) is allowed.  Element e = r * cols + c is
+ * kept iff word (e & 3) of Philox4x32-10(counter = (lo32(e >> 2), hi32(e >> 2), site, 0), key = (lo32(seed), hi32(seed))) is >= floor(p 2^32);
+ * a kept element becomes round((float)x * (float)(1 / (1 - p))), a dropped one 0.  The mask depends on (seed, site, e, p) only -- not on the
+ * pitches, the launch or the stream -- so the backward is the same call on dy with the same (seed, site, p), and no mask is stored.
+ * p = 1: all zeros; p = 0: a copy (nothing when x == y).  cols % 4 == 0; p outside [0, 1], ld < cols or NULL pointers: a negative code. */
+int mlpk_dropout(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, double p, uint64_t seed, uint32_t site, void* stream);
+
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that
  * product) -- the better plan when several forwards share the chip (parallel.InFlight) and the other request fills the last round anyway.  Same K order per output

@@ -151,6 +151,8 @@ PROTOTYPES = {
     "mlpk_split_softmax_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mlpk_s2_shift2": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p]),
     "mlpk_convert": (c_int, [c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
+    # (dtype, x, ldx, y, ldy, rows, cols, p, seed, site, stream)
+    "mlpk_dropout": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
 }
 
 _lib = None

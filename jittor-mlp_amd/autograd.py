@@ -10,6 +10,7 @@ derivative below is a call through the C ABI:
     LayerNorm             mlpk_row_stats + mlpk_norm_apply / mlpk_layernorm_backward (+ mlpk_col_sum for d gamma, d beta)
     token <-> channel     mlpk_transpose_batched (the residual add of the token-mixing block rides on the way back)
     token mean            mlpk_pool_mean / mlpk_broadcast_rows
+    Dropout               mlpk_dropout, forward and backward the same call (a Philox mask of (seed, site, element): nothing is stored)
 
 Used by the train-mode forward of MLPMixerForImageClassification (mlp_mixer.py:30-75); inference keeps its fused kernels.  Parameter
 gradients come back in fp32 whatever the compute dtype (the GEMMs accumulate in fp32 and round dW once to the compute dtype).
@@ -843,6 +844,31 @@ class AddPeriodic(torch.autograd.Function):
         with E.on_device(dy):
             dt = col_sum(dy.view(Bn, L * dy.shape[1]), Bn, L * dy.shape[1])
         return dy, dt.reshape(tshape), None
+
+
+class Dropout(torch.autograd.Function):
+    """nn.Dropout in train mode on (M, C) rows: mlpk_dropout's Philox mask of (seed, site, p) (mlpk.h).  Dropout is linear, so the backward is
+    the same call on dy: the tape holds p, seed and site, never a mask."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, site):
+        ctx.meta = (float(p), int(seed), int(site))
+        x = _rows(x)
+        y = torch.empty((x.shape[0], x.shape[1]), dtype=x.dtype, device=x.device)
+        return E.dropout(x, y, x.shape[0], x.shape[1], p, seed, site)
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, site = ctx.meta
+        dy = _rows(dy)
+        dx = torch.empty((dy.shape[0], dy.shape[1]), dtype=dy.dtype, device=dy.device)
+        return E.dropout(dy, dx, dy.shape[0], dy.shape[1], p, seed, site), None, None, None
+
+
+def dropout(t, p, seed, site):
+    """t unchanged where the rate is 0 (eval, or nn.Dropout(0)), else Dropout.apply"""
+    p = float(p)
+    return t if p == 0.0 else Dropout.apply(t, p, seed, site)
 
 
 def drop_add(owner, t, z, rate, B, period):

@@ -5,6 +5,7 @@
 // (mlp_mixer.py:34: dense = Conv1d over the patch axis), Reduce('b n c -> b c', 'mean') (mlp_mixer.py:63), and BatchNorm2d's batch
 // statistics (conv_mixer.py:20,28,31).  All HBM-bound; none of them is on the inference path.  fp32 math, one rounding per stored value.
 #include "mlpk_common.h"
+#include "mlpk_philox.h"
 
 namespace mlpk {
 
@@ -387,6 +388,73 @@ static unsigned ew_grid(int64_t total) {
     return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g));
 }
 
+// element m of a register chunk held as dwords (fp32: one per dword; 16-bit types: two, element 2k in the low half)
+template <typename T> __device__ __forceinline__ T get_bits(const uint32_t* q, int m) {
+    if constexpr (sizeof(T) == 4) {
+        return __builtin_bit_cast(T, q[m]);
+    } else {
+        return __builtin_bit_cast(T, (uint16_t)(q[m >> 1] >> (16 * (m & 1))));
+    }
+}
+template <typename T> __device__ __forceinline__ void set_bits(uint32_t* q, int m, T v) {
+    if constexpr (sizeof(T) == 4) {
+        q[m] = __builtin_bit_cast(uint32_t, v);
+    } else {
+        const uint32_t b = __builtin_bit_cast(uint16_t, v);
+        q[m >> 1] = (m & 1) ? (q[m >> 1] & 0xFFFFu) | (b << 16) : (q[m >> 1] & 0xFFFF0000u) | b;
+    }
+}
+
+// nn.Dropout in train mode (mlpk.h mlpk_dropout): y = keep ? x * scale : 0 with the keep bit a pure function of (seed, site, e, thr), e the
+// LOGICAL index r * cols + c -- the pitch, the grid and the vector width never enter it.  A lane takes a chunk of EPC elements of one row
+// (cols % EPC == 0): EPC = 16 / sizeof(T) with one 16-byte load and store (one Philox call per 4 fp32, two per 8 bf16 / fp16), or EPC = 4
+// with element loads where the rows are not 16-byte aligned.  CONTIG: both pitches equal cols, so e is the address offset (no division).
+// x and y may be the same buffer (no __restrict__): every lane reads its chunk before it stores it.
+template <typename T, int EPC, bool CONTIG>
+__global__ void __launch_bounds__(256) dropout_kernel(const T* x, int64_t ldx, T* y, int64_t ldy, int64_t rows, int cols,
+                                                      uint64_t seed, uint32_t site, uint64_t thr, float scale) {
+    constexpr bool VEC16 = EPC * sizeof(T) == 16;
+    const int64_t cpr = cols / EPC;
+    const int64_t total = rows * cpr;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        int64_t e, ox, oy;
+        if (CONTIG) {
+            e = ox = oy = i * EPC;
+        } else {
+            const int64_t r = i / cpr;
+            const int64_t c = (i - r * cpr) * EPC;
+            e = r * cols + c;
+            ox = r * ldx + c;
+            oy = r * ldy + c;
+        }
+        // the chunk as EPC 32-bit lanes' worth of values: 16-bit elements two to a dword (element 2k in the low half)
+        uint32_t q[EPC * sizeof(T) / 4];
+        if (VEC16) {
+            const uint4 u = *reinterpret_cast<const uint4*>(x + ox);
+            q[0] = u.x, q[1] = u.y, q[2] = u.z, q[3] = u.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < EPC; ++k) set_bits<T>(q, k, x[ox + k]);
+        }
+#pragma unroll
+        for (int j = 0; j < EPC / 4; ++j) {
+            const philox4 w = dropout_words(seed, site, (uint64_t)(e >> 2) + j);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int m = 4 * j + k;
+                const float v = (uint64_t)w.v[k] >= thr ? to_f32<T>(get_bits<T>(q, m)) * scale : 0.f;
+                set_bits<T>(q, m, from_f32<T>(v));
+            }
+        }
+        if (VEC16) {
+            *reinterpret_cast<uint4*>(y + oy) = make_uint4(q[0], q[1], q[2], q[3]);
+        } else {
+#pragma unroll
+            for (int k = 0; k < EPC; ++k) y[oy + k] = get_bits<T>(q, k);
+        }
+    }
+}
+
 }  // namespace mlpk
 
 #define BW_DISPATCH(DT, CALL_F32, CALL_F16, CALL_BF16) \
@@ -650,6 +718,39 @@ extern "C" int mlpk_index_gather(int dtype, const void* src, void* dst, const in
 #define IG(TT) hipLaunchKernelGGL((index_gather_kernel<TT>), dim3(g), dim3(256), 0, s, (const TT*)src, (TT*)dst, idx, batch, n_out, n_in, width, kmax)
     BW_DISPATCH(dtype, IG(float), IG(f16_t), IG(bf16_t))
 #undef IG
+    MLPK_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int mlpk_dropout(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, double p, uint64_t seed, uint32_t site,
+                            void* stream) {
+    using namespace mlpk;
+    if (!x || !y) return MLPK_ENULL;
+    if (!(p >= 0.0 && p <= 1.0)) return MLPK_ESHAPE;                                  // (NaN included)
+    if (rows <= 0 || cols <= 0 || cols % 4 != 0 || ldx < cols || ldy < cols || (x == y && ldx != ldy)) return MLPK_ESHAPE;
+    if (dtype != MLPK_F32 && dtype != MLPK_F16 && dtype != MLPK_BF16) return MLPK_EDTYPE;
+    if (p == 0.0 && x == y) return 0;                                                  // identity in place: nothing to do
+    const uint64_t thr = (uint64_t)floor(p * 4294967296.0);                           // p = 1: 2^32, above every word -- all dropped
+    const float scale = p < 1.0 ? (float)(1.0 / (1.0 - p)) : 0.f;
+    const int esz = dtype == MLPK_F32 ? 4 : 2;
+    const bool vec16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) && (cols * esz) % 16 == 0 && (ldx * esz) % 16 == 0 && (ldy * esz) % 16 == 0;
+    const bool contig = ldx == cols && ldy == cols;
+    const int epc = vec16 ? 16 / esz : 4;
+    int64_t g = (rows * (int64_t)(cols / epc) + 255) / 256;
+    g = g < 1 ? 1 : (g > 4096 ? 4096 : g);                                             // grid-stride: up to 16 waves per CU on 256 CUs
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+#define DK(TT, E, C) hipLaunchKernelGGL((dropout_kernel<TT, E, C>), dim3((unsigned)g), dim3(256), 0, s, (const TT*)x, ldx, (TT*)y, ldy, rows, cols, seed, site, thr, scale)
+#define DKT(TT)                                          \
+    if (vec16) {                                         \
+        if (contig) DK(TT, 16 / sizeof(TT), true);       \
+        else DK(TT, 16 / sizeof(TT), false);             \
+    } else {                                             \
+        if (contig) DK(TT, 4, true);                     \
+        else DK(TT, 4, false);                           \
+    }
+    BW_DISPATCH(dtype, DKT(float), DKT(f16_t), DKT(bf16_t))
+#undef DKT
+#undef DK
     MLPK_LAUNCH_CHECK();
     return 0;
 }

@@ -364,6 +364,14 @@ def add_periodic(x, ldx, table, rows, C, period):
     N.check(N.lib().mlpk_add_periodic(dtype_code(x.dtype), ptr(x), ldx, ptr(table), rows, C, period, stream()), "mlpk_add_periodic")
 
 
+def dropout(x, y, rows, cols, p, seed, site):
+    """y = dropout(x) on logical (rows, cols) rows (row strides x.stride(0) / y.stride(0); y may be x): mlpk_dropout's mask of (seed, site, p)"""
+    with on_device(x):
+        N.check(N.lib().mlpk_dropout(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(y), y.stride(0), rows, cols, float(p), int(seed) & (2 ** 64 - 1),
+                                     int(site) & 0xFFFFFFFF, stream()), "mlpk_dropout")
+    return y
+
+
 def rows_to_nchw(cur, B, HW, C, out):
     """channel-last rows (B*HW, C) -> (B, C, HW): mlpk_transpose_batched (the layout a reference module returns its maps in)"""
     N.check(N.lib().mlpk_transpose_batched(dtype_code(cur.dtype), ptr(cur), C, ptr(out), HW, None, 0, B, HW, C, stream()), "mlpk_transpose_batched")

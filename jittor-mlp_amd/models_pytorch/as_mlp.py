@@ -18,7 +18,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, SubModule, finalize_stats, head_linear, two_layer_mlp
+from .common import Block, Holder, SubModule, TrainDropout, finalize_stats, head_linear, two_layer_mlp
 from .utils.shift import Shift
 
 # GroupNorm(1,C) statistics from the producing GEMMs' epilogues (mlpk.h row_part, per-sample groups).  Off by default: measured
@@ -199,16 +199,18 @@ def _gn_params(norm, device):
     return E.f32(norm.weight, device), E.f32(norm.bias, device)
 
 
-class AS_MLP(E.EngineModule):
+class AS_MLP(TrainDropout, E.EngineModule):
     """Same signature and defaults as the reference (as_mlp.py:368-373).
 
     train() (round 5): the forward applies the blocks' stochastic depth (as_mlp.py:144,159-160: DropPath in front of both residual
     additions) -- per sample, branch * floor(keep + u) / keep with u uniform in [0, 1), the algorithm of timm's drop_path as the reference
     repository itself restates it (conv_mlp.py:17-34; timm is not vendored) -- as a per-row scale in the epilogue of the GEMM that adds the
     residual (mlpk.h: v * rscale[m] in front of + R).  The draws come from `drop_path_uniform(B, dtype, device)` (default torch.rand on the
-    input's device, one call per DropPath in the reference's order); GroupNorm has no batch statistics, Dropout has p = 0.  Forward only:
-    the outputs carry no grad_fn under torch.no_grad().  Round 6: with gradients enabled, train() runs `_forward_train` -- every step an
-    autograd.Function whose forward and backward are C-ABI calls -- and loss.backward() fills every parameter's .grad."""
+    input's device, one call per DropPath in the reference's order); GroupNorm has no batch statistics.  Forward only: the outputs carry no
+    grad_fn under torch.no_grad().  Round 6: with gradients enabled, train() runs `_forward_train` -- every step an autograd.Function whose
+    forward and backward are C-ABI calls -- and loss.backward() fills every parameter's .grad.  Dropout (drop_rate: pos_drop and the two
+    Mlp.drop of every block, as_mlp.py:16-23,391,430) runs there too -- see common.TrainDropout -- and train() takes that path under
+    torch.no_grad() as well whenever a rate is > 0; with every rate 0 the fused path runs as before."""
     _train_forward = True
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=[2, 2, 6, 2],
@@ -523,7 +525,8 @@ class AS_MLP(E.EngineModule):
         convolutions = mlpk_gemm_nt (dX, dW as GEMMs on transposed operands), GroupNorm(1, C) = mlpk_row_stats + mlpk_norm_apply /
         mlpk_group_norm_backward, GELU = mlpk_gelu_elementwise, the two axial shifts = mlpk_shift_nhwc / mlpk_shift_nhwc_backward (the
         reference's shift_backward_grad_input_kernel, utils/shift_cuda.py:75-103, on the channel-last layout), PatchMerging's gather =
-        mlpk_merge2x2_nhwc and its adjoint, stochastic depth = a per-sample row scale (as_mlp.py:55-95,118-162,197-216,428-443).
+        mlpk_merge2x2_nhwc and its adjoint, stochastic depth = a per-sample row scale, Dropout = mlpk_dropout on the channel-last rows
+        (as_mlp.py:8-24,55-95,118-162,197-216,428-443).
         Unfused on purpose: the pre-activations and normalised tensors are what the backward needs.  No gradient w.r.t. the input image."""
         from .. import autograd as AG
         E.require_gpu(x, "AS_MLP.forward")
@@ -556,9 +559,15 @@ class AS_MLP(E.EngineModule):
             scale = (torch.floor(keep + u.reshape(B).float()) / keep).contiguous()
             return AG.ScaleAdd.apply(t, AG.RowScale.apply(z, scale, HW), None)
 
+        def rate(drop):
+            return float(drop.p) if self.training else 0.0
+
+        seed = self.dropout_seed() if self._dropout_active() else 0
         t = conv(patches, pe.proj)
         if pe.norm is not None:
             t = gn(t, pe.norm)
+        t = AG.dropout(t, rate(self.pos_drop), seed, 0)                                      # pos_drop (as_mlp.py:430)
+        j = 0
         for layer in self.layers:
             HW = H * W
             for blk in layer.blocks:
@@ -569,8 +578,16 @@ class AS_MLP(E.EngineModule):
                 x_td = AG.Gelu.apply(conv(AG.ShiftNHWC.apply(u, B, H, W, self._shift, 2), a.conv2_2))
                 s = gn(AG.ScaleAdd.apply(x_lr, x_td, None), a.norm2)
                 t = add_dropped(t, conv(s, a.conv3), blk, HW) if dropped else conv(s, a.conv3, t)
-                h = AG.Gelu.apply(conv(gn(t, blk.norm2), blk.mlp.fc1))
-                t = add_dropped(t, conv(h, blk.mlp.fc2), blk, HW) if dropped else conv(h, blk.mlp.fc2, t)
+                # x + drop_path(drop(fc2(drop(gelu(fc1(norm2(x))))))) (as_mlp.py:16-23,160)
+                p_mlp = rate(blk.mlp.drop)
+                h = AG.dropout(AG.Gelu.apply(conv(gn(t, blk.norm2), blk.mlp.fc1)), p_mlp, seed, 1 + 2 * j)
+                if dropped:
+                    t = add_dropped(t, AG.dropout(conv(h, blk.mlp.fc2), p_mlp, seed, 2 + 2 * j), blk, HW)
+                elif p_mlp > 0.0:
+                    t = AG.ScaleAdd.apply(t, AG.dropout(conv(h, blk.mlp.fc2), p_mlp, seed, 2 + 2 * j), None)
+                else:
+                    t = conv(h, blk.mlp.fc2, t)
+                j += 1
             if layer.downsample is not None:
                 assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
                 ds = layer.downsample
@@ -582,8 +599,11 @@ class AS_MLP(E.EngineModule):
         logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
         return logits if logits.dtype == x.dtype else logits.to(x.dtype)
 
+    def _dropout_modules(self):
+        return [self.pos_drop] + [blk.mlp.drop for layer in self.layers for blk in layer.blocks]
+
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed

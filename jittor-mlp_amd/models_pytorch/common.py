@@ -1,5 +1,7 @@
 """Building blocks shared by the drop-in models: each helper issues the HIP kernels for one
 reference sub-module on channel-last activations held in a Workspace."""
+import warnings
+
 import torch
 from torch import nn
 
@@ -251,6 +253,40 @@ class StochasticDepth:
         u = self.drop_path_uniform(B, dtype, device)
         mask = torch.floor(keep + u.reshape(B).float())
         return (mask / keep).repeat_interleave(rows_per_sample).contiguous()
+
+
+class TrainDropout:
+    """Train-mode nn.Dropout of the families whose constructors take a drop_rate (Swin-MLP, AS-MLP, MS-MLP): autograd.Dropout -- mlpk_dropout's
+    counter-based mask, a pure function of (seed, site, element, p) -- at the reference's sites.  One seed per train-mode forward with any rate
+    > 0, from `dropout_seed()` (default: 63 bits from torch's CPU generator -- no device sync, and torch.manual_seed reproduces a run; tests
+    replace it).  Sites: 0 = pos_drop; the j-th block in forward order over all stages: 1 + 2j after the hidden GELU, 2 + 2j after fc2.
+    The rates are read from the modules at every forward (`.p`), as nn.Dropout does."""
+
+    def dropout_seed(self):
+        return int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
+
+    def _dropout_modules(self):
+        """the model's nn.Dropout modules in site order (a module may serve two sites)"""
+        raise NotImplementedError
+
+    def _dropout_active(self):
+        return self.training and any(float(m.p) > 0.0 for m in self._dropout_modules())
+
+
+def warn_unapplied_dropout(model):
+    """Train paths without Dropout (families whose constructors expose no rate): a RuntimeWarning, once per module, for every nn.Dropout
+    with p > 0 the path does not apply -- reachable by building blocks directly or by mutating `.p`."""
+    mods = model.__dict__.get("_dropout_list")
+    if mods is None:
+        mods = model.__dict__["_dropout_list"] = [(n, m) for n, m in model.named_modules() if isinstance(m, nn.Dropout)]
+    if not mods:
+        return
+    warned = model.__dict__.setdefault("_dropout_warned", set())
+    for name, m in mods:
+        if float(m.p) > 0.0 and name not in warned:
+            warned.add(name)
+            warnings.warn("%s: train mode does not apply %s.%s (nn.Dropout with p = %g): it runs as the identity" % (
+                type(model).__name__, type(model).__name__, name, float(m.p)), RuntimeWarning, stacklevel=3)
 
 
 def channel_mlp(ws, x, rows, C, pk, prefix, hidden, *, norm=True, cscale2=None, res_src=None, tag="cm", eps=1e-5, stats=None, part=None, rscale=None):

@@ -26,7 +26,7 @@ from torch.nn import init
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, LinearMlp, StochasticDepth, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp
+from .common import Block, Holder, LinearMlp, StochasticDepth, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp, warn_unapplied_dropout
 from .utils import pair
 
 
@@ -376,6 +376,7 @@ class CycleNet(StochasticDepth, E.EngineModule):
         the reweighting = per-image means, two small Linears, the softmax over the three branches (mlpk_split_softmax + backward) and the weighted
         sum (mlpk_ew_cols); stochastic depth and 1 / skip_lam as per-sample / per-channel scales; Downsample (3 x 3 stride 2) = an
         overlapping-window table + mlpk_gemm_nt.  (deform_conv2d itself: the stand-in caveat of SURVEY 8f-3 applies to the fixture, not to this code.)"""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "CycleNet.forward")
         if x.dim() != 4:

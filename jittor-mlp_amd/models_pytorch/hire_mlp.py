@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, BlockSequential, Holder, SubModule, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp
+from .common import Block, BlockSequential, Holder, SubModule, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp, warn_unapplied_dropout
 from .utils import pair
 
 
@@ -379,6 +379,7 @@ class HireMLP(E.EngineModule):
         patterns on a tensor of positions; the inverse table -- which sums the duplicates the circular padding makes -- is the gradient);
         the region FeedForwards and proj_c are mlpk_gemm_nt (proj_c is pointwise: it commutes with the padding and the crop); the 3 x 3
         stride-2 stage transitions are an overlapping-window table + mlpk_gemm_nt (col2im = the inverse table)."""
+        warn_unapplied_dropout(self)
         import torch.nn.functional as F
         from .. import autograd as AG
         E.require_gpu(x, "HireMLP.forward")

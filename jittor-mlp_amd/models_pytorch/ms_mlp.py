@@ -14,7 +14,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, StochasticDepth, SubModule, channel_mlp, embed_patches, finalize_stats, head_linear, layernorm_stats
+from .common import Block, Holder, StochasticDepth, SubModule, TrainDropout, channel_mlp, embed_patches, finalize_stats, head_linear, layernorm_stats
 
 MS_EPS = 1e-6
 
@@ -123,11 +123,13 @@ class BasicLayer(Block):
             self.downsample = None
 
 
-class MS_MLP(StochasticDepth, E.EngineModule):
+class MS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
     """Same signature and defaults as the reference (ms_mlp.py:300-306).
 
     train() (round 6): the forward applies the blocks' stochastic depth (ms_mlp.py:46,77: x = input + drop_path(gamma * branch)) --
-    see common.StochasticDepth; the LayerNorms have no batch statistics, Dropout has p = 0.  Forward only: the outputs carry no grad_fn."""
+    see common.StochasticDepth; the LayerNorms have no batch statistics.  Dropout (drop_rate: pos_drop, ms_mlp.py:314,354 -- the blocks' `drop`
+    is unused in the reference too) runs in `_forward_train` -- see common.TrainDropout -- which train() also takes under torch.no_grad()
+    whenever the rate is > 0; with rate 0 the fused path runs as before.  Forward only: the outputs carry no grad_fn."""
     _train_forward = True
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=[2, 2, 6, 2], shift_size=5,
@@ -306,7 +308,7 @@ class MS_MLP(StochasticDepth, E.EngineModule):
         granularity, built by running torch.roll on a tensor of positions; the inverse table is the gradient); the per-chunk depthwise
         convolutions of different sizes run as ONE depthwise convolution whose taps are the chunks' kernels zero-padded to the largest size
         (mlpk_dwconv_plain_nhwc; the padding and concatenation of the small weight tensors are torch views autograd maps back); layer scale =
-        mlpk_ew_cols; stochastic depth on drop_path_uniform's draws; the stage transitions (Conv2d 2 x 2 stride 2 + LayerNorm) =
+        mlpk_ew_cols; stochastic depth on drop_path_uniform's draws; pos_drop = mlpk_dropout (common.TrainDropout); the stage transitions (Conv2d 2 x 2 stride 2 + LayerNorm) =
         mlpk_patch_rows_nhwc + mlpk_gemm_nt."""
         import torch.nn.functional as F
         from .. import autograd as AG
@@ -334,6 +336,8 @@ class MS_MLP(StochasticDepth, E.EngineModule):
         t = AG.Linear.apply(patches, pe.proj.weight, pe.proj.bias, None)
         if pe.norm is not None:
             t = ln(t, pe.norm)
+        if self._dropout_active():
+            t = AG.dropout(t, self.pos_drop.p, self.dropout_seed(), 0)                       # pos_drop (ms_mlp.py:354)
         C = self.embed_dim
         for layer in self.layers:
             for blk in layer.blocks:
@@ -377,8 +381,11 @@ class MS_MLP(StochasticDepth, E.EngineModule):
         logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
         return logits if logits.dtype == x.dtype else logits.to(x.dtype)
 
+    def _dropout_modules(self):
+        return [self.pos_drop]
+
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed

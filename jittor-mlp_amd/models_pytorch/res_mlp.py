@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, SubModule, adopt_blocks, embed_patches, head_linear, two_layer_mlp
+from .common import Block, Holder, SubModule, adopt_blocks, embed_patches, head_linear, two_layer_mlp, warn_unapplied_dropout
 from .utils.tools import check_sizes, pair
 
 
@@ -221,6 +221,7 @@ class ResMLPForImageClassification(ResMLP):
         through the C ABI -- Aff and the layer scales gamma_1 / gamma_2 = mlpk_ew_cols (parameter gradients: mlpk_col_dot / mlpk_col_sum), the
         cross-patch Conv1d(k=1) and the FeedForward = mlpk_gemm_nt (+ the two GEMMs of their backward) between mlpk_transpose_batched rearranges.
         The model-level `affine` takes no part in forward (res_mlp.py:86,91-99): its parameters get no gradient, as in the reference."""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "ResMLPForImageClassification.forward")
         if x.dim() != 4:

@@ -9,7 +9,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import PreNormResidualMLP, BlockSequential, Holder, channel_mlp, finalize_stats, head_linear, layernorm_stats, stage_embed, pack_channel_mlp
+from .common import PreNormResidualMLP, BlockSequential, Holder, channel_mlp, finalize_stats, head_linear, layernorm_stats, stage_embed, pack_channel_mlp, warn_unapplied_dropout
 from .s2_mlp_v2 import SHIFT_MODES
 from .utils.tools import pair
 
@@ -169,6 +169,7 @@ class S2MLPv1(E.EngineModule):
         """Train mode with autograd (round 6): s2_mlp_v1.py:6-93 as autograd.Functions of `..autograd` (see S2MLPv2._forward_train): the
         Spatial_Shift between the two Linears of the token-mixing sublayer runs in the model's shift_mode forward and returns the gradient the
         reference's autograd returns for the in-place slice assignments (the adjoint of the intended shift)."""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "S2MLPv1.forward")
         if x.dim() != 4:

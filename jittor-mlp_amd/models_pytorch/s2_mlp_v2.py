@@ -21,7 +21,7 @@ from torch import nn
 from .. import _native as N
 from .. import engine as E
 from .common import (PreNormResidualMLP, BlockSequential, Holder, channel_mlp, finalize_stats, head_linear, layernorm_stats, split_attention_forward,
-                     split_attention_weights, standalone_space, stage_embed, pack_channel_mlp)
+                     split_attention_weights, standalone_space, stage_embed, pack_channel_mlp, warn_unapplied_dropout)
 from .utils.tools import pair
 
 SHIFT_MODES = {"reference_inplace": N.SHIFT_S2_REF, "shift": N.SHIFT_S2}
@@ -259,6 +259,7 @@ class S2MLPv2(E.EngineModule):
         shift_mode (default: the reference's in-place result), the backward what the reference's autograd returns for those assignments -- the
         adjoint of the INTENDED shift (mlpk_s2_shift2, checked against the reference's own gradients).  Stage convolutions after the first read
         the previous stage's channel-last rows (mlpk_patch_rows_nhwc and its inverse for the gradient that flows back)."""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "S2MLPv2.forward")
         if x.dim() != 4:

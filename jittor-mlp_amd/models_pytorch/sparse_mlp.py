@@ -24,7 +24,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, BlockSequential, Holder, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp
+from .common import Block, BlockSequential, Holder, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp, warn_unapplied_dropout
 from .conv_mixer import _bn_affine
 from .utils import pair
 
@@ -353,6 +353,7 @@ class SparseMLP(E.EngineModule):
         PreNormResidual(norm = BatchNorm2d) sublayers); proj_h / proj_w contract over H resp. W: the ViP rearranges with one-channel segments
         (mlpk_norm_apply out_ph / out_pw, mlpk_vip_unpermute) around mlpk_gemm_nt; the concatenation in front of `fuse` = column slices of one
         buffer; the depthwise 3 x 3 = mlpk_dwconv_plain_nhwc (+ adjoint, + mlpk_dwconv_wgrad_nhwc); PatchMerging = mlpk_merge2x2_nhwc."""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "SparseMLP.forward")
         if x.dim() != 4:

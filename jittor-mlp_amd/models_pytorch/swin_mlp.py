@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, LinearMlp, StochasticDepth, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp
+from .common import Block, Holder, LinearMlp, StochasticDepth, TrainDropout, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp
 
 
 def to_2tuple(v):
@@ -106,12 +106,14 @@ class PatchEmbed(Block):
         self.norm = norm_layer(embed_dim) if norm_layer is not None else None
 
 
-class SwinMLP(StochasticDepth, E.EngineModule):
+class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
     """Same signature and defaults as the reference (swin_mlp.py:374-379).
 
     train() (round 6): the forward applies the blocks' stochastic depth (swin_mlp.py:105,154-155: the same DropPath in front of
-    both residual additions of a block) -- see common.StochasticDepth; LayerNorm has no batch statistics, Dropout has p = 0.  Forward only:
-    the outputs carry no grad_fn."""
+    both residual additions of a block) -- see common.StochasticDepth; LayerNorm has no batch statistics.  Dropout (drop_rate: pos_drop and the
+    two Mlp.drop of every block, swin_mlp.py:23-30,390,437-439) runs in `_forward_train` -- see common.TrainDropout -- which train() also takes
+    under torch.no_grad() whenever a rate is > 0; with every rate 0 the fused path below runs as before.  Forward only: the outputs carry no
+    grad_fn."""
     _train_forward = True
 
     def __init__(self, img_size=224, patch_size=4, in_chans=3, num_classes=1000, embed_dim=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24],
@@ -324,11 +326,12 @@ class SwinMLP(StochasticDepth, E.EngineModule):
             return cur.reshape(B, H * W, C).clone()
 
     def _forward_train(self, x):
-        """Train mode with autograd (round 6): swin_mlp.py:33-157,175-215,295-335,428-456 as autograd.Functions of `..autograd`,
+        """Train mode with autograd (round 6): swin_mlp.py:12-30,33-157,175-215,295-335,428-456 as autograd.Functions of `..autograd`,
         forward and backward through the C ABI.  The zero padding of the shifted blocks, the window partition and their inverses are index
         tables (mlpk_index_gather; the inverse table is the gradient), built by running the reference's own F.pad / view / permute on a tensor
         of positions; the multi-head spatial MLP (a grouped Conv1d over a window's tokens) is one mlpk_gemm_nt per head between per-window
-        transposes (mlpk_transpose_batched); stochastic depth on drop_path_uniform's draws; PatchMerging = mlpk_merge2x2_nhwc."""
+        transposes (mlpk_transpose_batched); stochastic depth on drop_path_uniform's draws; Dropout = mlpk_dropout on dropout_seed()'s seed
+        (common.TrainDropout); PatchMerging = mlpk_merge2x2_nhwc."""
         import torch.nn.functional as F
         from .. import autograd as AG
         E.require_gpu(x, "SwinMLP.forward")
@@ -357,7 +360,14 @@ class SwinMLP(StochasticDepth, E.EngineModule):
             t = ln(t, pe.norm)
         if self.ape:
             t = AG.AddPeriodic.apply(t, self.absolute_pos_embed, H * W)
+
+        def rate(drop):
+            return float(drop.p) if self.training else 0.0
+
+        seed = self.dropout_seed() if self._dropout_active() else 0
+        t = AG.dropout(t, rate(self.pos_drop), seed, 0)                                      # pos_drop (swin_mlp.py:439)
         C = self.embed_dim
+        j = 0
         for layer in self.layers:
             for blk in layer.blocks:
                 ws, nH = blk.window_size, blk.num_heads
@@ -387,11 +397,15 @@ class SwinMLP(StochasticDepth, E.EngineModule):
                     heads.append(AG.RowsToTokens.apply(AG.Linear.apply(rows_h, wgt, bias, None), nwb, ws * ws, ch))
                 y = AG.IndexMap.apply(AG.ConcatCols.apply(*heads) if nH > 1 else heads[0], t_rev, B, C)
                 t = AG.drop_add(self, t, y, blk.drop_path_rate if self.training else 0.0, B, H * W)
-                hdn = AG.Gelu.apply(AG.Linear.apply(ln(t, blk.norm2), blk.mlp.fc1.weight, blk.mlp.fc1.bias, None))
-                if float(blk.drop_path_rate) > 0.0:
-                    t = AG.drop_add(self, t, AG.Linear.apply(hdn, blk.mlp.fc2.weight, blk.mlp.fc2.bias, None), blk.drop_path_rate, B, H * W)
+                # x + drop_path(drop(fc2(drop(gelu(fc1(norm2(x))))))) (swin_mlp.py:23-30,155)
+                p_mlp = rate(blk.mlp.drop)
+                hdn = AG.dropout(AG.Gelu.apply(AG.Linear.apply(ln(t, blk.norm2), blk.mlp.fc1.weight, blk.mlp.fc1.bias, None)), p_mlp, seed, 1 + 2 * j)
+                if float(blk.drop_path_rate) > 0.0 or p_mlp > 0.0:
+                    z = AG.dropout(AG.Linear.apply(hdn, blk.mlp.fc2.weight, blk.mlp.fc2.bias, None), p_mlp, seed, 2 + 2 * j)
+                    t = AG.drop_add(self, t, z, blk.drop_path_rate, B, H * W)
                 else:
                     t = AG.Linear.apply(hdn, blk.mlp.fc2.weight, blk.mlp.fc2.bias, t)
+                j += 1
             if layer.downsample is not None:
                 ds = layer.downsample
                 t = AG.Linear.apply(ln(AG.Merge2x2.apply(t, B, H, W), ds.norm), ds.reduction.weight, None, None)
@@ -402,8 +416,11 @@ class SwinMLP(StochasticDepth, E.EngineModule):
         logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
         return logits if logits.dtype == x.dtype else logits.to(x.dtype)
 
+    def _dropout_modules(self):
+        return [self.pos_drop] + [blk.mlp.drop for layer in self.layers for blk in layer.blocks]
+
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed

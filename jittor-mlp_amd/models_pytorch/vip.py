@@ -19,7 +19,7 @@ from torch import nn
 from .. import _native as N
 from .. import engine as E
 from .common import (PreNormResidualMLP, BlockSequential, Holder, adopt_blocks, channel_mlp, embed_patches, finalize_stats, head_linear, layernorm_stats,
-                     split_attention_forward, split_attention_weights, standalone_space, pack_channel_mlp)
+                     split_attention_forward, split_attention_weights, standalone_space, pack_channel_mlp, warn_unapplied_dropout)
 from .utils.tools import pair
 
 
@@ -372,6 +372,7 @@ class ViP(E.EngineModule):
         the einops rearranges = mlpk_norm_apply(out_ph / out_pw) and mlpk_vip_unpermute (each the other's backward), SplitAttention = per-image
         sums (mlpk_pool_mean / mlpk_broadcast_rows), two small Linears, mlpk_split_softmax (+ _backward) and the weighted sum by mlpk_ew_cols
         (weights' gradient: mlpk_col_dot_seg); ParallelSum (weighted=False) = two mlpk_ew_cols additions."""
+        warn_unapplied_dropout(self)
         from .. import autograd as AG
         E.require_gpu(x, "ViP.forward")
         if x.dim() != 4:
