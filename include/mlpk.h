@@ -58,6 +58,7 @@
  *                       LDS); the reduction of ViP's SplitAttention needs no pass at all: mlpk_norm_desc.sum_ph / sum_pw + linearity
  *   mlpk_vip_branch     LayerNorm + rearrange + Linear of ViP's h / w branch in ONE kernel, the rearrange as LDS staging order (vip.py:66-76)
  *   mlpk_s2_shift       Spatial_Shift (s2_mlp_v1.py:19-25), out of place
+ *   mlpk_wave_patm      WaveMLP's PATM phase modulation + both grouped 7-tap convolutions (wave_mlp.py:46-60) in one pass
  *   mlpk_dwconv_nhwc    depthwise Conv2d(k, groups=dim, padding="same") + GELU + BatchNorm(eval) + residual:
  *                       conv_mixer.py:5-11,24-28
  */
@@ -731,6 +732,20 @@ int mlpk_index_gather(int dtype, const void* src, void* dst, const int* idx, int
  * pitches, the launch or the stream -- so the backward is the same call on dy with the same (seed, site, p), and no mask is stored.
  * p = 1: all zeros; p = 0: a copy (nothing when x == y).  cols % 4 == 0; p outside [0, 1], ld < cols or NULL pointers: a negative code. */
 int mlpk_dropout(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int cols, double p, uint64_t seed, uint32_t site, void* stream);
+
+/* WaveMLP's phase-aware token mixing (PATM, wave_mlp.py:46-60) after its five 1 x 1 convolutions, in one pass.  y: channel-last rows of the (B, H, W)
+ * map, row stride ldy >= 5C, holding [theta_h | theta_w | x_h | x_w | c] (theta before its ReLU; c is not read).  With P[j] = x[j mod C] *
+ * (j < C ? cos : sin)(relu(theta[j mod C])) for the 2C concatenated channels of each branch, the grouped convolutions (groups = C) give
+ *   out_h[b,y,x,g] = sum_{k<7} wh[g][0][k] P_h[b,y,x+k-3][2g] + wh[g][1][k] P_h[b,y,x+k-3][2g+1]      (tfc_h: kernel (1,7), padding (0,3))
+ *   out_w[b,y,x,g] = sum_{k<7} ww[g][0][k] P_w[b,y+k-3,x][2g] + ww[g][1][k] P_w[b,y+k-3,x][2g+1]      (tfc_w: kernel (7,1), padding (3,0))
+ * zero outside the map: output g < C/2 is the cos of source channels 2g, 2g+1, output g >= C/2 the sin of 2g-C, 2g-C+1.  wh, ww: fp32 (C, 2, 7),
+ * the Conv2d weights (C, 2, 1, 7) / (C, 2, 7, 1) as they lie.  sincos in fp32 with full range reduction, products and sums in fp32, one rounding at
+ * the store; out_h / out_w rows of stride ldo (they may be two column slices of one buffer, not overlapping y).  Any map size (1 x 1 included).
+ * Errors: NULL pointer MLPK_ENULL; unknown dtype MLPK_EDTYPE; B, H, W, C <= 0, C % 4 != 0, ldy < 5C or ldo < C MLPK_ESHAPE; y or ldy not aligned to
+ * 4 elements, out_h / out_w or ldo not aligned to 2 elements MLPK_EALIGN.  mlpk_wave_patm_supported: 1 when the dtype and shape are taken, else 0. */
+int mlpk_wave_patm_supported(int dtype, int B, int H, int W, int C);
+int mlpk_wave_patm(int dtype, const void* y, int64_t ldy, const float* wh, const float* ww, void* out_h, void* out_w, int64_t ldo, int B, int H, int W,
+                   int C, void* stream);
 
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that

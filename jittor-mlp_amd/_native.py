@@ -153,6 +153,9 @@ PROTOTYPES = {
     "mlpk_convert": (c_int, [c_int, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     # (dtype, x, ldx, y, ldy, rows, cols, p, seed, site, stream)
     "mlpk_dropout": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_int, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, c_void_p]),
+    "mlpk_wave_patm_supported": (c_int, [c_int] * 5),
+    # (dtype, y, ldy, wh, ww, out_h, out_w, ldo, B, H, W, C, stream)
+    "mlpk_wave_patm": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64] + [c_int] * 4 + [c_void_p]),
 }
 
 _lib = None

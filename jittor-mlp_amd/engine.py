@@ -797,6 +797,17 @@ def split_sum(x0, x1, x2, ld0, ld1, ld2, B, H, W, C, mode, a, scale=1.0):
                                    scale, ptr(a), stream()), "mlpk_split_sum")
 
 
+def wave_patm_supported(dtype, B, H, W, C):
+    return bool(N.lib().mlpk_wave_patm_supported(dtype_code(dtype), B, H, W, C))
+
+
+def wave_patm(y, wh, ww, out_h, out_w, B, H, W, C):
+    """WaveMLP's PATM core (mlpk_wave_patm): y = rows [theta_h | theta_w | x_h | x_w | c] -> out_h, out_w (the two grouped 7-tap convolutions of the
+    phase-modulated x_h / x_w); wh / ww fp32 (C, 2, 7).  out_h and out_w share one row stride."""
+    N.check(N.lib().mlpk_wave_patm(dtype_code(y.dtype), ptr(y), y.stride(0), ptr(wh), ptr(ww), ptr(out_h), ptr(out_w), out_h.stride(0), B, H, W, C,
+                                   stream()), "mlpk_wave_patm")
+
+
 def split_softmax(hat, bar, B, C):
     N.check(N.lib().mlpk_split_softmax(ptr(hat), ptr(bar), B, C, stream()), "mlpk_split_softmax")
 
