@@ -2229,9 +2229,18 @@ extern "C" int mlpk_gemm_nt(const mlpk_gemm_desc* d, void* stream) {
 extern "C" int mlpk_conv_gemm_nhwc_supported(int dtype, int Cin, int kh, int kw, int stride, int pad);
 extern "C" int mlpk_conv_gemm_nhwc(const mlpk_gemm_desc* d, int B, int H, int W, int Cin, int kh, int kw, int stride, int pad, void* stream);
 
+// conv_src divides n < n_max by d with one multiply by m = ceil(2^16 / d) and a 16-bit shift: kt / cpk (n_max = kh kw cpk) and tap / kw
+// (n_max = kh kw).  With e = m d - 2^16 that is exact for every n < n_max iff (n_max - 1) e < 2^16 (n_max is a multiple of d, so n_max - 1
+// has the worst remainder, d - 1).  Shapes that fail it are refused rather than divided wrongly (7 x 7, Cin 1536: cpk 48, e 32, kt 2351 gave
+// tap 49); the model call sites (2 x 2 and 3 x 3, Cin <= 768) all pass, and the kernel's code is unchanged.
+static bool conv_div_exact(long long n_max, long long d) {
+    const long long m = (65536 + d - 1) / d;
+    return (n_max - 1) * (m * d - 65536) < 65536;
+}
+
 extern "C" int mlpk_conv_gemm_nhwc_supported(int dtype, int Cin, int kh, int kw, int stride, int pad) {
     return (dtype == MLPK_F16 || dtype == MLPK_BF16) && Cin >= 32 && Cin % 32 == 0 && kh >= 1 && kw >= 1 && kh * kw <= 49 && stride >= 1 && pad >= 0 && pad < kh &&
-           pad < kw && (long long)kh * kw * (Cin / 32) < 65536;
+           pad < kw && (long long)kh * kw * (Cin / 32) < 65536 && conv_div_exact((long long)kh * kw * (Cin / 32), Cin / 32) && conv_div_exact(kh * kw, kw);
 }
 
 template <typename T>

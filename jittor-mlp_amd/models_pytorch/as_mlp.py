@@ -541,7 +541,7 @@ class AS_MLP(TrainDropout, E.EngineModule):
         ph, pw = pe.patch_size
         H, W = H_in // ph, W_in // pw
         dev = x.device
-        kp = E.round_up(cin * ph * pw, 4 if cd == torch.float32 else 8)
+        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
         with E.on_device(x):
             patches = torch.zeros((B * H * W, kp), dtype=cd, device=dev)
             E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)

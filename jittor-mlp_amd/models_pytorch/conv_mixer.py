@@ -178,7 +178,7 @@ class ConvMixer(E.EngineModule):
         pad = patch // 2
         H, W = (H_in + 2 * pad - patch) // patch + 1, (W_in + 2 * pad - patch) // patch + 1
         rows = B * H * W
-        kp = E.round_up(cin * patch * patch, 4 if cd == torch.float32 else 8)
+        kp = E.round_up(cin * patch * patch, 8)        # (mlpk_patchify: ldo % 8 == 0 in every dtype)
         with E.on_device(x):
             patches = torch.zeros((rows, kp), dtype=cd, device=x.device)
             E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, patch, patch, pad, kp)

@@ -234,7 +234,7 @@ class ResMLPForImageClassification(ResMLP):
         if (H // ph) * (W // pw) != S:
             raise ValueError("input size gives %d patches, the model was built for %d" % ((H // ph) * (W // pw), S))
         conv = self.patcher[0]
-        kp = E.round_up(cin * ph * pw, 4 if cd == torch.float32 else 8)
+        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
         with E.on_device(x):
             patches = torch.zeros((B * S, kp), dtype=cd, device=x.device)
             E.patchify(x.contiguous(), patches, B, cin, H, W, ph, pw, 0, kp)

@@ -183,7 +183,7 @@ class S2MLPv1(E.EngineModule):
             conv, blk = self.stages[s][0], self.stages[s][1]
             ph, pw = self._patches[s]
             if s == 0:
-                kp = E.round_up(cin * ph * pw, 4 if cd == torch.float32 else 8)
+                kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
                 with E.on_device(x):
                     patches = torch.zeros((B * (H // ph) * (W // pw), kp), dtype=cd, device=x.device)
                     E.patchify(x.contiguous(), patches, B, cin, H, W, ph, pw, 0, kp)

@@ -366,7 +366,7 @@ class SparseMLP(E.EngineModule):
         H, W = H_in // ph, W_in // pw
         if (H, W) != self.layers[0].geom[:2]:
             raise ValueError("input size gives a %dx%d grid, the model was built for %dx%d" % ((H, W) + self.layers[0].geom[:2]))
-        kp = E.round_up(cin * ph * pw, 4 if cd == torch.float32 else 8)
+        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
         with E.on_device(x):
             patches = torch.zeros((B * H * W, kp), dtype=cd, device=x.device)
             E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)

@@ -387,7 +387,7 @@ class ViP(E.EngineModule):
         if (H_in // ph, W_in // pw) != (H, W):
             raise ValueError("input size gives a %dx%d grid, the model was built for %dx%d" % (H_in // ph, W_in // pw, H, W))
         conv = self.patcher[0]
-        kp = E.round_up(cin * ph * pw, 4 if cd == torch.float32 else 8)
+        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
         S = H * W
         with E.on_device(x):
             patches = torch.zeros((B * S, kp), dtype=cd, device=x.device)

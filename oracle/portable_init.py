@@ -100,3 +100,11 @@ def portable_state_dict(shapes, seed=0):
         else:
             out[key] = portable_tensor(key, shape, -0.1, 0.1, seed)
     return out
+
+
+def portable_signs(name, n, k=8, seed=0):
+    """k x n float64 matrix of +-1 (Rademacher), row i = bit i of one portable 53-bit draw per column: k seeded random directions, cheap
+    enough to project a multi-million-entry gradient on both sides of a fixture (E <e, r_i>^2 = |e|^2 for any vector e)."""
+    assert 1 <= k <= 53
+    bits = (_uniform01(name, n, seed, stream=3) * float(1 << 53)).astype(np.uint64)
+    return np.stack([1.0 - 2.0 * ((bits >> np.uint64(i)) & np.uint64(1)).astype(np.float64) for i in range(k)])

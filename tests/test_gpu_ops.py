@@ -1406,6 +1406,16 @@ def test_conv_gemm_nhwc_is_im2col_plus_gemm(dtype):
         if part_g is not None:
             assert part_g[1] == part_w[1] and torch.equal(part_g[0], part_w[0]), (str(dtype), ci)
     assert not E.conv_gemm_nhwc_supported(dtype, 48, 3, 3, 2, 1) and not E.conv_gemm_nhwc_supported(torch.float32, 64, 3, 3, 2, 1)
+    # 7 x 7 at Cin = 1536 passed the old bound, but the loader's slab divide was wrong there (kt 2351 -> tap 49, not 48; test_host_cpu.py
+    # brute-forces every accepted shape): refused now, and the launcher writes nothing
+    assert not E.conv_gemm_nhwc_supported(dtype, 1536, 7, 7, 1, 3)
+    x = rnd((8 * 8, 1536), dtype, 1930).to(dev())
+    w = (rnd((64, 49 * 1536), dtype, 1931) / 256).to(dtype).to(dev())
+    got = torch.full((8 * 8, 64), float("nan"), dtype=dtype, device=dev())
+    with pytest.raises(N.MlpkError, match="mlpk_conv_gemm_nhwc"):
+        E.conv_gemm_nhwc(x, w, got, 1, 8, 8, 1536, 7, 7, 1, 3)
+    torch.cuda.synchronize()
+    assert torch.isnan(got.float()).all()
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])

@@ -412,3 +412,39 @@ def test_linear_gelu_and_swin_packing_orders(pkg):
     assert tuple(sw.shape) == (heads, 64, 64) and tuple(sb.shape) == (heads, 64)
     assert torch.equal(sw[:, :t, :t], cw.reshape(heads, t, t).to(torch.bfloat16)) and not sw[:, t:].any() and not sw[:, :, t:].any()
     assert torch.equal(sb[:, :t], cb.reshape(heads, t)) and not sb[:, t:].any()
+
+
+def test_conv_gemm_nhwc_divides_exactly_for_every_accepted_shape():
+    """mlpk_conv_gemm_nhwc's operand loader divides by one multiply and a 16-bit shift (mlpk_gemm.hip conv_src): tap = (kt m_cpk) >> 16 for
+    every slab kt < kh kw cpk (cpk = Cin / 32), dy = (tap m_kw) >> 16 for every tap < kh kw, m_d = ceil(2^16 / d).  Brute force, in integers,
+    over every (kh, kw, Cin) that mlpk_conv_gemm_nhwc_supported accepts up to its limits (kh kw <= 49, kh kw cpk < 2^16): every quotient
+    exact.  The bound alone accepted 7 x 7 with Cin = 1536 (cpk 48, m 1366): kt = 2351 gave tap 49 instead of 48.  The model call sites
+    (2 x 2 and 3 x 3 windows, Cin <= 768) stay accepted."""
+    import numpy as np
+    N = load_pkg()._native
+    ok = N.lib().mlpk_conv_gemm_nhwc_supported
+    n_max, kws, accepted = {}, set(), 0
+    for kh in range(1, 50):
+        for kw in range(1, 49 // kh + 1):
+            cpk = 1
+            while kh * kw * cpk < 65536:
+                if ok(N.F16, 32 * cpk, kh, kw, 1, 0):
+                    assert ok(N.BF16, 32 * cpk, kh, kw, 1, 0)
+                    n_max[cpk] = max(n_max.get(cpk, 0), kh * kw * cpk)
+                    kws.add((kh, kw))
+                    accepted += 1
+                cpk += 1
+    assert accepted > 1000
+    # exactness for n < N implies it for every smaller N: one pass per divisor up to its largest accepted n
+    for d, top in n_max.items():
+        n = np.arange(top, dtype=np.int64)
+        assert np.array_equal((n * ((65536 + d - 1) // d)) >> 16, n // d), ("kt / cpk", d, top)
+        assert top * ((65536 + d - 1) // d) < 2 ** 31                          # (the kernel multiplies in int32)
+    for kh, kw in kws:
+        n = np.arange(kh * kw, dtype=np.int64)
+        assert np.array_equal((n * ((65536 + kw - 1) // kw)) >> 16, n // kw), ("tap / kw", kh, kw)
+    assert (2351 * ((65536 + 47) // 48)) >> 16 == 49 and 7 * 7 * 48 > 2351     # the case the bound alone let through ...
+    assert not ok(N.F16, 1536, 7, 7, 1, 3) and not ok(N.BF16, 1536, 7, 7, 1, 3)  # ... is refused now
+    for cin in range(32, 769, 32):
+        for k, st, pad in ((3, 2, 1), (3, 1, 1), (2, 2, 0)):
+            assert ok(N.F16, cin, k, k, st, pad) and ok(N.BF16, cin, k, k, st, pad), (cin, k)
