@@ -883,6 +883,58 @@ def drop_add(owner, t, z, rate, B, period):
     return ScaleAdd.apply(t, RowScale.apply(z, scale, period), None)
 
 
+# ---- the train-mode forwards' building blocks, each on the torch module it stands for -------------------------------------------------
+def linear(t, mod, res=None):
+    """mod(t) (+ res) for an nn.Linear / Conv1d(k=1) / Conv2d(k=1) whose weight and bias are used as they are"""
+    return Linear.apply(t, mod.weight, mod.bias, res)
+
+
+def mlp(t, fc1, fc2, res=None):
+    """fc2(gelu(fc1(t))) (+ res)"""
+    return linear(Gelu.apply(linear(t, fc1)), fc2, res)
+
+
+def layer_norm(t, norm):
+    return LayerNorm.apply(t, norm.weight, norm.bias, norm.eps)
+
+
+def group_norm1(t, norm, B):
+    return GroupNorm1.apply(t, norm.weight, norm.bias, B, norm.eps)
+
+
+def batch_norm_train(t, bn):
+    """nn.BatchNorm2d in train mode on channel-last rows: the batch statistics, the running-statistics update, BatchNormTrain"""
+    rows, cols = t.shape
+    mean, var = batch_stats(t.detach(), rows, cols)
+    batchnorm_train_affine(bn, mean, var, rows)
+    return BatchNormTrain.apply(t, bn.weight, bn.bias, mean, var, bn.eps)
+
+
+def drop_mlp_add(owner, t, n, mlp_mod, rate, p, seed, site, B, period):
+    """t + drop_path(drop(fc2(drop(gelu(fc1(n)))))) on n = norm2(t): the Mlp sublayer of Swin-MLP and AS-MLP (swin_mlp.py:23-30,155;
+    as_mlp.py:16-23,160), Dropout sites `site` and `site + 1`; with neither rate > 0, fc2 adds the residual in its epilogue"""
+    h = dropout(Gelu.apply(linear(n, mlp_mod.fc1)), p, seed, site)
+    if float(rate) > 0.0 or p > 0.0:
+        return drop_add(owner, t, dropout(linear(h, mlp_mod.fc2), p, seed, site + 1), rate, B, period)
+    return linear(h, mlp_mod.fc2, t)
+
+
+def conv_rows(x, conv, cd):
+    """nn.Conv2d on the NCHW image x -> (channel-last rows (B * Ho * Wo, Cout) in dtype cd, Ho, Wo): the patch gather (mlpk_patchify when
+    kernel_size == stride, else mlpk_im2col; rows zero-padded to whole 8-element chunks, as both require) + Linear"""
+    B, cin, H, W = x.shape
+    (kh, kw), (sh, sw), pad = conv.kernel_size, conv.stride, conv.padding[0]
+    Ho, Wo = (H + 2 * pad - kh) // sh + 1, (W + 2 * pad - kw) // sw + 1
+    kp = E.round_up(cin * kh * kw, 8)
+    with E.on_device(x):
+        patches = torch.zeros((B * Ho * Wo, kp), dtype=cd, device=x.device)
+        if (kh, kw) == (sh, sw):
+            E.patchify(x.contiguous(), patches, B, cin, H, W, kh, kw, pad, kp)
+        else:
+            E.im2col(x.contiguous(), patches, B, cin, H, W, kh, kw, sh, sw, pad, kp)
+    return linear(patches, conv), Ho, Wo
+
+
 def position_table(fn, n_in, width, device, cache, key):
     """IndexTable of a remap given as torch index arithmetic: fn(pos) is applied to a float64 tensor of source positions + 1 (0 = padding)
     and returns the destination layout; cached per key"""

@@ -1009,6 +1009,10 @@ class EngineModule(torch.nn.Module):
             self._spaces[key] = ws
         return ws
 
+    def _train_path(self):
+        """whether forward() takes the family's `_forward_train` (the autograd path)"""
+        return self.training and torch.is_grad_enabled()
+
     def _resolve(self, x):
         require_gpu(x, type(self).__name__ + ".forward")
         if x.dim() != 4:
@@ -1019,11 +1023,6 @@ class EngineModule(torch.nn.Module):
             warnings.warn("%s is inference-only: forward() ignores train mode (Dropout / DropPath are identity, BatchNorm uses "
                           "its running statistics) and the outputs carry no grad_fn; call .eval()" % type(self).__name__,
                           stacklevel=3)
-            self.__dict__["_warned_train"] = True
-        elif self.training and not self._warned_train and getattr(self, "_train_forward", False) == "forward-only":
-            import warnings
-            warnings.warn("%s.train(): the train-mode FORWARD is implemented (batch statistics / stochastic depth), the backward is not -- "
-                          "the outputs carry no grad_fn and a frozen sub-module contributes no gradients" % type(self).__name__, stacklevel=3)
             self.__dict__["_warned_train"] = True
         cd = self._compute_dtype or x.dtype
         dtype_code(cd)

@@ -18,7 +18,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, SubModule, TrainDropout, finalize_stats, head_linear, two_layer_mlp
+from .common import Block, Holder, StochasticDepth, SubModule, TrainDropout, finalize_stats, head_linear, train_entry, two_layer_mlp
 from .utils.shift import Shift
 
 # GroupNorm(1,C) statistics from the producing GEMMs' epilogues (mlpk.h row_part, per-sample groups).  Off by default: measured
@@ -199,15 +199,12 @@ def _gn_params(norm, device):
     return E.f32(norm.weight, device), E.f32(norm.bias, device)
 
 
-class AS_MLP(TrainDropout, E.EngineModule):
+class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
     """Same signature and defaults as the reference (as_mlp.py:368-373).
 
     train() (round 5): the forward applies the blocks' stochastic depth (as_mlp.py:144,159-160: DropPath in front of both residual
-    additions) -- per sample, branch * floor(keep + u) / keep with u uniform in [0, 1), the algorithm of timm's drop_path as the reference
-    repository itself restates it (conv_mlp.py:17-34; timm is not vendored) -- as a per-row scale in the epilogue of the GEMM that adds the
-    residual (mlpk.h: v * rscale[m] in front of + R).  The draws come from `drop_path_uniform(B, dtype, device)` (default torch.rand on the
-    input's device, one call per DropPath in the reference's order); GroupNorm has no batch statistics.  Forward only: the outputs carry no
-    grad_fn under torch.no_grad().  Round 6: with gradients enabled, train() runs `_forward_train` -- every step an autograd.Function whose
+    additions) -- see common.StochasticDepth; GroupNorm has no batch statistics.  Forward only: the outputs carry no grad_fn under
+    torch.no_grad().  Round 6: with gradients enabled, train() runs `_forward_train` -- every step an autograd.Function whose
     forward and backward are C-ABI calls -- and loss.backward() fills every parameter's .grad.  Dropout (drop_rate: pos_drop and the two
     Mlp.drop of every block, as_mlp.py:16-23,391,430) runs there too -- see common.TrainDropout -- and train() takes that path under
     torch.no_grad() as well whenever a rate is > 0; with every rate 0 the fused path runs as before."""
@@ -249,11 +246,6 @@ class AS_MLP(TrainDropout, E.EngineModule):
             if layer.downsample is not None:
                 layer.downsample.__dict__["_owner"] = (self, (li, "down"))
         self.patch_embed.__dict__["_owner"] = (self, ("embed", None))
-
-    def drop_path_uniform(self, B, dtype, device):
-        """the uniform draws of one DropPath call in train mode (a method, so that the module pickles; tests replace it per instance
-        with the reference run's recorded draws)"""
-        return torch.rand((B,), dtype=dtype, device=device)
 
     def _init_weights(self, m):
         # as_mlp.py:419-426: only nn.Linear (= the head) gets the truncated normal
@@ -322,16 +314,6 @@ class AS_MLP(TrainDropout, E.EngineModule):
         E.norm_apply(x, B * HW, C, C, mean=mean, rstd=rstd, gamma=g, beta=b, act=act, stat_group=HW, out_rm=out, ld_rm=C)
         return out
 
-    def _drop_scale(self, blk, B, HW, dtype, device):
-        """Per-row scale of one DropPath call in train mode (None: identity): conv_mlp.py:27-34 per sample, repeated over the sample's rows."""
-        rate = float(blk.drop_path_rate)
-        if not self.training or rate == 0.0:
-            return None
-        keep = 1.0 - rate
-        u = self.drop_path_uniform(B, dtype, device)
-        mask = torch.floor(keep + u.reshape(B).float())
-        return (mask / keep).repeat_interleave(HW).contiguous()
-
     def _run_layers(self, ws, pk, cur, B, H, W, C, cd, only=None):
         """The stages on channel-last rows `cur` (B*H*W, C).  only = (layer, block): that one block alone, on a `cur` that already has
         the layer's resolution and width (AxialShiftedBlock called on its own).  Returns (cur, H, W, C, have, mean, rstd)."""
@@ -394,12 +376,12 @@ class AS_MLP(TrainDropout, E.EngineModule):
                     if st2 is None:
                         stats(t1, C, got)
                         st2 = (mean, rstd)
-                    dp1 = self._drop_scale(layer.blocks[bi], B, HW, cd, cur.device)                 # train mode: x + drop_path(.) (as_mlp.py:159)
+                    dp1 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)  # train mode: x + drop_path(.) (as_mlp.py:159)
                     got = E.gemm(t1, pk[p + "c3f.w"], cur, rows, C, C, bias=pk[p + "c3f.b"], ln=(st2[0], st2[1], pk[p + "c3f.csum"]), ln_group=HW,
                                  R=cur, res=N.RES_ADD, tag="as_conv", part=part if dp1 is None else None,
                                  rscale=dp1, rperiod=rows if dp1 is not None else 0)                 # x + conv3(norm2(.))
                     stats(cur, C, got)
-                    dp2 = self._drop_scale(layer.blocks[bi], B, HW, cd, cur.device)                 # ... x + drop_path(mlp(norm2(x))) (:160)
+                    dp2 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)  # ... x + drop_path(mlp(norm2(x))) (:160)
                     if dp2 is not None:
                         E.gemm(cur, pk[p + "fc1f.w"], hbuf, rows, hid, C, bias=pk[p + "fc1f.b"], act=N.ACT_GELU,
                                ln=(mean, rstd, pk[p + "fc1f.csum"]), ln_group=HW, tag="as_fc1")
@@ -428,12 +410,12 @@ class AS_MLP(TrainDropout, E.EngineModule):
                 E.gemm(t0, pk[p + "c22.w"], t2, rows, C, C, bias=pk[p + "c22.b"], act=N.ACT_GELU, R=t2, res=N.RES_ADD,
                        tag="as_conv")                                                                # gelu(.) + x_lr
                 self._gn(ws, tag, t2, B, HW, C, pk[p + "an2.g"], pk[p + "an2.b"], t2)
-                dp1 = self._drop_scale(layer.blocks[bi], B, HW, cd, cur.device)
+                dp1 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)
                 E.gemm(t2, pk[p + "c3.w"], cur, rows, C, C, bias=pk[p + "c3.b"], R=cur, res=N.RES_ADD, tag="as_conv",
                        rscale=dp1, rperiod=rows if dp1 is not None else 0)
                 self._gn(ws, tag, cur, B, HW, C, pk[p + "n2.g"], pk[p + "n2.b"], t0)                 # norm2(x)
                 E.gemm(t0, pk[p + "fc1.w"], hbuf, rows, hid, C, bias=pk[p + "fc1.b"], act=N.ACT_GELU, tag="as_fc1")
-                dp2 = self._drop_scale(layer.blocks[bi], B, HW, cd, cur.device)
+                dp2 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)
                 E.gemm(hbuf, pk[p + "fc2.w"], cur, rows, C, hid, bias=pk[p + "fc2.b"], R=cur, res=N.RES_ADD, tag="as_fc2",
                        rscale=dp2, rperiod=rows if dp2 is not None else 0)
             if layer.downsample is not None and (only is None or only[1] in ("layer", "down")):
@@ -529,41 +511,20 @@ class AS_MLP(TrainDropout, E.EngineModule):
         (as_mlp.py:8-24,55-95,118-162,197-216,428-443).
         Unfused on purpose: the pre-activations and normalised tensors are what the backward needs.  No gradient w.r.t. the input image."""
         from .. import autograd as AG
-        E.require_gpu(x, "AS_MLP.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
+        cd = train_entry(self, x)
         pe = self.patch_embed
-        B, cin, H_in, W_in = x.shape
+        B, _, H_in, W_in = x.shape
         assert H_in == pe.img_size[0] and W_in == pe.img_size[1], \
             f"Input image size ({H_in}*{W_in}) doesn't match model ({pe.img_size[0]}*{pe.img_size[1]})."
-        ph, pw = pe.patch_size
-        H, W = H_in // ph, W_in // pw
-        dev = x.device
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * H * W, kp), dtype=cd, device=dev)
-            E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)
 
         def gn(t, norm):
-            return AG.GroupNorm1.apply(t, norm.weight, norm.bias, B, norm.eps)
-
-        def conv(t, c, res=None):
-            return AG.Linear.apply(t, c.weight, c.bias, res)
-
-        def add_dropped(t, z, blk, HW):
-            # x + drop_path(z) (as_mlp.py:159-160); rate 0 / eval: handled by the callers through the GEMM's residual epilogue
-            keep = 1.0 - float(blk.drop_path_rate)
-            u = self.drop_path_uniform(B, cd, dev)
-            scale = (torch.floor(keep + u.reshape(B).float()) / keep).contiguous()
-            return AG.ScaleAdd.apply(t, AG.RowScale.apply(z, scale, HW), None)
+            return AG.group_norm1(t, norm, B)
 
         def rate(drop):
             return float(drop.p) if self.training else 0.0
 
         seed = self.dropout_seed() if self._dropout_active() else 0
-        t = conv(patches, pe.proj)
+        t, H, W = AG.conv_rows(x, pe.proj, cd)
         if pe.norm is not None:
             t = gn(t, pe.norm)
         t = AG.dropout(t, rate(self.pos_drop), seed, 0)                                      # pos_drop (as_mlp.py:430)
@@ -572,38 +533,31 @@ class AS_MLP(TrainDropout, E.EngineModule):
             HW = H * W
             for blk in layer.blocks:
                 a = blk.axial_shift
-                dropped = float(blk.drop_path_rate) > 0.0
-                u = AG.Gelu.apply(gn(conv(gn(t, blk.norm1), a.conv1), a.norm1))
-                x_lr = AG.Gelu.apply(conv(AG.ShiftNHWC.apply(u, B, H, W, self._shift, 3), a.conv2_1))
-                x_td = AG.Gelu.apply(conv(AG.ShiftNHWC.apply(u, B, H, W, self._shift, 2), a.conv2_2))
+                u = AG.Gelu.apply(gn(AG.linear(gn(t, blk.norm1), a.conv1), a.norm1))
+                x_lr = AG.Gelu.apply(AG.linear(AG.ShiftNHWC.apply(u, B, H, W, self._shift, 3), a.conv2_1))
+                x_td = AG.Gelu.apply(AG.linear(AG.ShiftNHWC.apply(u, B, H, W, self._shift, 2), a.conv2_2))
                 s = gn(AG.ScaleAdd.apply(x_lr, x_td, None), a.norm2)
-                t = add_dropped(t, conv(s, a.conv3), blk, HW) if dropped else conv(s, a.conv3, t)
-                # x + drop_path(drop(fc2(drop(gelu(fc1(norm2(x))))))) (as_mlp.py:16-23,160)
-                p_mlp = rate(blk.mlp.drop)
-                h = AG.dropout(AG.Gelu.apply(conv(gn(t, blk.norm2), blk.mlp.fc1)), p_mlp, seed, 1 + 2 * j)
-                if dropped:
-                    t = add_dropped(t, AG.dropout(conv(h, blk.mlp.fc2), p_mlp, seed, 2 + 2 * j), blk, HW)
-                elif p_mlp > 0.0:
-                    t = AG.ScaleAdd.apply(t, AG.dropout(conv(h, blk.mlp.fc2), p_mlp, seed, 2 + 2 * j), None)
+                if float(blk.drop_path_rate) > 0.0:
+                    t = AG.drop_add(self, t, AG.linear(s, a.conv3), blk.drop_path_rate, B, HW)       # x + drop_path(.) (as_mlp.py:159)
                 else:
-                    t = conv(h, blk.mlp.fc2, t)
+                    t = AG.linear(s, a.conv3, t)
+                t = AG.drop_mlp_add(self, t, gn(t, blk.norm2), blk.mlp, blk.drop_path_rate, rate(blk.mlp.drop), seed, 1 + 2 * j, B, HW)
                 j += 1
             if layer.downsample is not None:
                 assert H % 2 == 0 and W % 2 == 0, f"x size ({H}*{W}) are not even."
                 ds = layer.downsample
-                t = conv(gn(AG.Merge2x2.apply(t, B, H, W), ds.norm), ds.reduction)
+                t = AG.linear(gn(AG.Merge2x2.apply(t, B, H, W), ds.norm), ds.reduction)
                 H, W = H // 2, W // 2
         pooled = AG.TokenMean.apply(gn(t, self.norm), B, H * W)
         if not isinstance(self.head, nn.Linear):
-            return pooled if pooled.dtype == x.dtype else pooled.to(x.dtype)
-        logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+            return pooled.to(x.dtype)
+        return AG.linear(pooled, self.head).to(x.dtype)
 
     def _dropout_modules(self):
         return [self.pos_drop] + [blk.mlp.drop for layer in self.layers for blk in layer.blocks]
 
     def forward(self, x):
-        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed

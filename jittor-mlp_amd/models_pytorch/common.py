@@ -272,6 +272,9 @@ class TrainDropout:
     def _dropout_active(self):
         return self.training and any(float(m.p) > 0.0 for m in self._dropout_modules())
 
+    def _train_path(self):
+        return super()._train_path() or self._dropout_active()
+
 
 def warn_unapplied_dropout(model):
     """Train paths without Dropout (families whose constructors expose no rate): a RuntimeWarning, once per module, for every nn.Dropout
@@ -286,7 +289,20 @@ def warn_unapplied_dropout(model):
         if float(m.p) > 0.0 and name not in warned:
             warned.add(name)
             warnings.warn("%s: train mode does not apply %s.%s (nn.Dropout with p = %g): it runs as the identity" % (
-                type(model).__name__, type(model).__name__, name, float(m.p)), RuntimeWarning, stacklevel=3)
+                type(model).__name__, type(model).__name__, name, float(m.p)), RuntimeWarning, stacklevel=4)
+
+
+def train_entry(model, x, warn_dropout=False):
+    """The checks every `_forward_train` opens with: warn_unapplied_dropout (warn_dropout: the families whose train path applies no Dropout),
+    a GPU tensor, a (B, C, H, W) input; returns the compute dtype"""
+    if warn_dropout:
+        warn_unapplied_dropout(model)
+    E.require_gpu(x, type(model).__name__ + ".forward")
+    if x.dim() != 4:
+        raise ValueError("expected a (B, C, H, W) tensor")
+    cd = model._compute_dtype or x.dtype
+    E.dtype_code(cd)
+    return cd
 
 
 def channel_mlp(ws, x, rows, C, pk, prefix, hidden, *, norm=True, cscale2=None, res_src=None, tag="cm", eps=1e-5, stats=None, part=None, rscale=None):

@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, adopt_blocks, embed_patches, finalize_stats, head_linear, layernorm_stats, standalone_space
+from .common import Block, Holder, adopt_blocks, embed_patches, finalize_stats, head_linear, layernorm_stats, standalone_space, train_entry
 from .utils.tools import check_sizes, pair
 
 
@@ -220,36 +220,23 @@ class gMLPForImageClassification(gMLP):
         = mlpk_row_stats + mlpk_norm_apply / mlpk_layernorm_backward (the SGU's on the v half of h IN PLACE: a row stride of 2 d_ffn), the
         gate u * v and its two derivatives = mlpk_ew_cols, the token <-> channel rearranges = mlpk_transpose_batched.  Unfused on purpose."""
         from .. import autograd as AG
-        E.require_gpu(x, "gMLPForImageClassification.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
-        S, C, F, _ = self._dims
-        B, cin, H, W = x.shape
+        cd = train_entry(self, x)
+        S, _, F, _ = self._dims
+        B, _, H, W = x.shape
         ph, pw = self._patch
         if (H // ph) * (W // pw) != S:
             raise ValueError("input size gives %d patches, the model was built for %d" % ((H // ph) * (W // pw), S))
-        conv = self.patcher[0]
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * S, kp), dtype=cd, device=x.device)
-            E.patchify(x.contiguous(), patches, B, cin, H, W, ph, pw, 0, kp)
-        t = AG.Linear.apply(patches, conv.weight, conv.bias, None)
+        t, _, _ = AG.conv_rows(x, self.patcher[0], cd)
         for blk in self.model:
-            n = AG.LayerNorm.apply(t, blk.norm.weight, blk.norm.bias, blk.norm.eps)
-            h = AG.Gelu.apply(AG.Linear.apply(n, blk.channel_proj1.weight, blk.channel_proj1.bias, None))            # (B*S, 2F)
+            h = AG.Gelu.apply(AG.linear(AG.layer_norm(t, blk.norm), blk.channel_proj1))                                # (B*S, 2F)
             u, v = h[:, :F], h[:, F:]                                                                                  # chunk(2, dim=-1): views
-            vn = AG.LayerNorm.apply(v, blk.sgu.norm.weight, blk.sgu.norm.bias, blk.sgu.norm.eps)
-            sp = blk.sgu.spatial_proj
-            vs = AG.RowsToTokens.apply(AG.Linear.apply(AG.TokensToRows.apply(vn, B, S), sp.weight, sp.bias, None), B, S, F)
-            t = AG.Linear.apply(AG.Mul.apply(u, vs), blk.channel_proj2.weight, blk.channel_proj2.bias, t)
-        head = self.mlp_head[0]
-        logits = AG.Linear.apply(AG.TokenMean.apply(t, B, S), head.weight, head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+            vs = AG.RowsToTokens.apply(AG.linear(AG.TokensToRows.apply(AG.layer_norm(v, blk.sgu.norm), B, S), blk.sgu.spatial_proj), B, S, F)
+            t = AG.linear(AG.Mul.apply(u, vs), blk.channel_proj2, t)
+        logits = AG.linear(AG.TokenMean.apply(t, B, S), self.mlp_head[0])
+        return logits.to(x.dtype)
 
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         S, C, _, _ = self._dims

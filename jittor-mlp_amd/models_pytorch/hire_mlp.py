@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, BlockSequential, Holder, SubModule, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp, warn_unapplied_dropout
+from .common import Block, BlockSequential, Holder, SubModule, channel_mlp, finalize_stats, head_linear, layernorm_stats, pack_channel_mlp, train_entry
 from .utils import pair
 
 
@@ -379,34 +379,16 @@ class HireMLP(E.EngineModule):
         patterns on a tensor of positions; the inverse table -- which sums the duplicates the circular padding makes -- is the gradient);
         the region FeedForwards and proj_c are mlpk_gemm_nt (proj_c is pointwise: it commutes with the padding and the crop); the 3 x 3
         stride-2 stage transitions are an overlapping-window table + mlpk_gemm_nt (col2im = the inverse table)."""
-        warn_unapplied_dropout(self)
         import torch.nn.functional as F
         from .. import autograd as AG
-        E.require_gpu(x, "HireMLP.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
-        patch, cin, num_classes, patcher_norm = self._cfg
-        B, _, H_in, W_in = x.shape
+        cd = train_entry(self, x, warn_dropout=True)
+        B = x.shape[0]
         dev = x.device
-        H, W = (H_in + 6 - 7) // patch[0] + 1, (W_in + 6 - 7) // patch[1] + 1
-        kp = E.round_up(cin * 49, 8)                                                     # (mlpk_im2col: rows of whole 16-byte chunks)
-        with E.on_device(x):
-            patches = torch.zeros((B * H * W, kp), dtype=cd, device=dev)
-            E.im2col(x.contiguous(), patches, B, cin, H_in, W_in, 7, 7, patch[0], patch[1], 3, kp)
         tables = self.__dict__.setdefault("_tables", {})
-
-        def ln(t, norm):
-            return AG.LayerNorm.apply(t, norm.weight, norm.bias, norm.eps)
-
-        def ff(rows, m):                                                                          # FeedForward (hire_mlp.py:33-42): two 1x1 convs
-            return AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(rows, m.net[0].weight, m.net[0].bias, None)), m.net[2].weight, m.net[2].bias, None)
-
         red = self.patcher.reduction
-        t = AG.Linear.apply(patches, red[0].weight, red[0].bias, None)
-        if patcher_norm:
-            t = ln(t, red[1][1])
+        t, H, W = AG.conv_rows(x, red[0], cd)
+        if self._cfg[3]:                                                                          # patcher_norm
+            t = AG.layer_norm(t, red[1][1])
         for stage in self.layers:
             h, w, C, Cout, depth, ef = stage.geom
             for blk in stage.model:
@@ -444,30 +426,27 @@ class HireMLP(E.EngineModule):
                     return g[:, :, :H, :W].permute(0, 2, 3, 1).contiguous()
 
                 key = (H, W, C, h, w, step, hb.padding_type)
-                if hb.padding_type in ("reflect", "replicate", "circular"):
-                    pass
                 th = AG.position_table(region_h, H * W * C, 1, dev, tables, ("rh",) + key)
                 tw = AG.position_table(region_w, H * W * C, 1, dev, tables, ("rw",) + key)
                 bh = AG.position_table(restore_h, Hp * Wp * C, 1, dev, tables, ("bh",) + key)
                 bw = AG.position_table(restore_w, Hp * Wp * C, 1, dev, tables, ("bw",) + key)
-                n = ln(t, pre.norm)
-                x_h = AG.IndexMap.apply(ff(AG.IndexMap.apply(n, th, B, C * h), hb.proj_h), bh, B, C)
-                x_w = AG.IndexMap.apply(ff(AG.IndexMap.apply(n, tw, B, C * w), hb.proj_w), bw, B, C)
-                x_c = AG.Linear.apply(n, hb.proj_c.weight, hb.proj_c.bias, None)
+                n = AG.layer_norm(t, pre.norm)
+                # the region FeedForwards (hire_mlp.py:33-42): two 1x1 convs
+                x_h = AG.IndexMap.apply(AG.mlp(AG.IndexMap.apply(n, th, B, C * h), hb.proj_h.net[0], hb.proj_h.net[2]), bh, B, C)
+                x_w = AG.IndexMap.apply(AG.mlp(AG.IndexMap.apply(n, tw, B, C * w), hb.proj_w.net[0], hb.proj_w.net[2]), bw, B, C)
+                x_c = AG.linear(n, hb.proj_c)
                 t = AG.ScaleAdd.apply(AG.ScaleAdd.apply(AG.ScaleAdd.apply(x_c, x_h, None), x_w, None), t, None)
-                fc1, fc2 = mlp.fn[0], mlp.fn[3]
-                t = AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(ln(t, mlp.norm), fc1.weight, fc1.bias, None)), fc2.weight, fc2.bias, t)
+                t = AG.mlp(AG.layer_norm(t, mlp.norm), mlp.fn[0], mlp.fn[3], t)
             if stage.pooling:
                 conv = stage.patch_merge[1].reduction[0]
                 tab = AG.conv_window_table(H, W, C, 3, 2, 1, dev, tables)
                 t = AG.Linear.apply(AG.IndexMap.apply(t, tab, B, 9 * C), conv.weight.permute(0, 2, 3, 1), conv.bias, None)
                 H, W = tab.out_hw
-        head_ln, head = self.mlp_head[0], self.mlp_head[2]
-        logits = AG.Linear.apply(AG.TokenMean.apply(ln(t, head_ln), B, H * W), head.weight, head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+        logits = AG.linear(AG.TokenMean.apply(AG.layer_norm(t, self.mlp_head[0]), B, H * W), self.mlp_head[2])
+        return logits.to(x.dtype)
 
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         patch, cin, num_classes, patcher_norm = self._cfg

@@ -14,7 +14,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, StochasticDepth, SubModule, TrainDropout, channel_mlp, embed_patches, finalize_stats, head_linear, layernorm_stats
+from .common import Block, Holder, StochasticDepth, SubModule, TrainDropout, channel_mlp, embed_patches, finalize_stats, head_linear, layernorm_stats, train_entry
 
 MS_EPS = 1e-6
 
@@ -312,30 +312,16 @@ class MS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
         mlpk_patch_rows_nhwc + mlpk_gemm_nt."""
         import torch.nn.functional as F
         from .. import autograd as AG
-        E.require_gpu(x, "MS_MLP.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
+        cd = train_entry(self, x)
         pe = self.patch_embed
-        B, cin, H_in, W_in = x.shape
+        B, _, H_in, W_in = x.shape
         assert H_in == pe.img_size[0] and W_in == pe.img_size[1], \
             f"Input image size ({H_in}*{W_in}) doesn't match model ({pe.img_size[0]}*{pe.img_size[1]})."
-        ph, pw = pe.patch_size
-        H, W = H_in // ph, W_in // pw
         dev = x.device
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * H * W, kp), dtype=cd, device=dev)
-            E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)
         tables = self.__dict__.setdefault("_tables", {})
-
-        def ln(t, norm):
-            return AG.LayerNorm.apply(t, norm.weight, norm.bias, norm.eps)
-
-        t = AG.Linear.apply(patches, pe.proj.weight, pe.proj.bias, None)
+        t, H, W = AG.conv_rows(x, pe.proj, cd)
         if pe.norm is not None:
-            t = ln(t, pe.norm)
+            t = AG.layer_norm(t, pe.norm)
         if self._dropout_active():
             t = AG.dropout(t, self.pos_drop.p, self.dropout_seed(), 0)                       # pos_drop (ms_mlp.py:354)
         C = self.embed_dim
@@ -364,8 +350,7 @@ class MS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                 w_td, b_td = taps(blk.dwconv_td)
                 x_lr = AG.DepthwiseConv.apply(AG.IndexMap.apply(t, t_lr, B, C), w_lr, b_lr, B, H, W)
                 x_td = AG.DepthwiseConv.apply(AG.IndexMap.apply(t, t_td, B, C), w_td, b_td, B, H, W)
-                n = ln(AG.ScaleAdd.apply(x_lr, x_td, None), blk.norm)
-                z = AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(n, blk.pwconv1.weight, blk.pwconv1.bias, None)), blk.pwconv2.weight, blk.pwconv2.bias, None)
+                z = AG.mlp(AG.layer_norm(AG.ScaleAdd.apply(x_lr, x_td, None), blk.norm), blk.pwconv1, blk.pwconv2)
                 if blk.gamma is not None:
                     z = AG.Affine.apply(z, blk.gamma, None)
                 t = AG.drop_add(self, t, z, blk.drop_path_rate, B, H * W)
@@ -373,19 +358,18 @@ class MS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                 ds = layer.downsample
                 t = AG.Linear.apply(AG.PatchRowsNHWC.apply(t, B, H, W, 2, 2), ds.proj.weight.permute(0, 2, 3, 1), ds.proj.bias, None)
                 if ds.norm is not None:
-                    t = ln(t, ds.norm)
+                    t = AG.layer_norm(t, ds.norm)
                 H, W, C = H // 2, W // 2, 2 * C
-        pooled = ln(AG.TokenMean.apply(t, B, H * W), self.norm)                               # avgpool, THEN the norm (ms_mlp.py:359-361)
+        pooled = AG.layer_norm(AG.TokenMean.apply(t, B, H * W), self.norm)                     # avgpool, THEN the norm (ms_mlp.py:359-361)
         if not isinstance(self.head, nn.Linear):
-            return pooled if pooled.dtype == x.dtype else pooled.to(x.dtype)
-        logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+            return pooled.to(x.dtype)
+        return AG.linear(pooled, self.head).to(x.dtype)
 
     def _dropout_modules(self):
         return [self.pos_drop]
 
     def forward(self, x):
-        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed

@@ -15,7 +15,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, SubModule, adopt_blocks, embed_patches, head_linear, two_layer_mlp, warn_unapplied_dropout
+from .common import Block, Holder, SubModule, adopt_blocks, embed_patches, head_linear, two_layer_mlp, train_entry
 from .utils.tools import check_sizes, pair
 
 
@@ -221,38 +221,24 @@ class ResMLPForImageClassification(ResMLP):
         through the C ABI -- Aff and the layer scales gamma_1 / gamma_2 = mlpk_ew_cols (parameter gradients: mlpk_col_dot / mlpk_col_sum), the
         cross-patch Conv1d(k=1) and the FeedForward = mlpk_gemm_nt (+ the two GEMMs of their backward) between mlpk_transpose_batched rearranges.
         The model-level `affine` takes no part in forward (res_mlp.py:86,91-99): its parameters get no gradient, as in the reference."""
-        warn_unapplied_dropout(self)
         from .. import autograd as AG
-        E.require_gpu(x, "ResMLPForImageClassification.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
+        cd = train_entry(self, x, warn_dropout=True)
         S, C, _, _ = self._dims
-        B, cin, H, W = x.shape
+        B, _, H, W = x.shape
         ph, pw = self._patch
         if (H // ph) * (W // pw) != S:
             raise ValueError("input size gives %d patches, the model was built for %d" % ((H // ph) * (W // pw), S))
-        conv = self.patcher[0]
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * S, kp), dtype=cd, device=x.device)
-            E.patchify(x.contiguous(), patches, B, cin, H, W, ph, pw, 0, kp)
-        t = AG.Linear.apply(patches, conv.weight, conv.bias, None)
+        t, _, _ = AG.conv_rows(x, self.patcher[0], cd)
         for blk in self.model:
             x1 = AG.Affine.apply(t, blk.pre_affine.alpha, blk.pre_affine.beta)
-            tm = blk.token_mix
-            z = AG.RowsToTokens.apply(AG.Linear.apply(AG.TokensToRows.apply(x1, B, S), tm.weight, tm.bias, None), B, S, C)
+            z = AG.RowsToTokens.apply(AG.linear(AG.TokensToRows.apply(x1, B, S), blk.token_mix), B, S, C)
             x3 = AG.Affine.apply(AG.ScaleAdd.apply(x1, z, blk.gamma_1), blk.post_affine.alpha, blk.post_affine.beta)
-            fc1, fc2 = blk.ff.net[0], blk.ff.net[3]
-            f = AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(x3, fc1.weight, fc1.bias, None)), fc2.weight, fc2.bias, None)
-            t = AG.ScaleAdd.apply(x3, f, blk.gamma_2)
-        head = self.mlp_head[0]
-        logits = AG.Linear.apply(AG.TokenMean.apply(t, B, S), head.weight, head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+            t = AG.ScaleAdd.apply(x3, AG.mlp(x3, blk.ff.net[0], blk.ff.net[3]), blk.gamma_2)
+        logits = AG.linear(AG.TokenMean.apply(t, B, S), self.mlp_head[0])
+        return logits.to(x.dtype)
 
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         S, C, _, _ = self._dims

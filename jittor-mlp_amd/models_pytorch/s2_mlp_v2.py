@@ -21,7 +21,7 @@ from torch import nn
 from .. import _native as N
 from .. import engine as E
 from .common import (PreNormResidualMLP, BlockSequential, Holder, channel_mlp, finalize_stats, head_linear, layernorm_stats, split_attention_forward,
-                     split_attention_weights, standalone_space, stage_embed, pack_channel_mlp, warn_unapplied_dropout)
+                     split_attention_weights, standalone_space, stage_embed, pack_channel_mlp, train_entry)
 from .utils.tools import pair
 
 SHIFT_MODES = {"reference_inplace": N.SHIFT_S2_REF, "shift": N.SHIFT_S2}
@@ -259,25 +259,16 @@ class S2MLPv2(E.EngineModule):
         shift_mode (default: the reference's in-place result), the backward what the reference's autograd returns for those assignments -- the
         adjoint of the INTENDED shift (mlpk_s2_shift2, checked against the reference's own gradients).  Stage convolutions after the first read
         the previous stage's channel-last rows (mlpk_patch_rows_nhwc and its inverse for the gradient that flows back)."""
-        warn_unapplied_dropout(self)
         from .. import autograd as AG
-        E.require_gpu(x, "S2MLPv2.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
-        B, cin, H, W = x.shape
+        cd = train_entry(self, x, warn_dropout=True)
+        B, _, H, W = x.shape
         smear = self.shift_mode == "reference_inplace"
         t = None
         for s in range(self.stage):
             conv, blk = self.stages[s][0], self.stages[s][1]
             ph, pw = self._patches[s]
             if s == 0:
-                kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-                with E.on_device(x):
-                    patches = torch.zeros((B * (H // ph) * (W // pw), kp), dtype=cd, device=x.device)
-                    E.patchify(x.contiguous(), patches, B, cin, H, W, ph, pw, 0, kp)
-                t = AG.Linear.apply(patches, conv.weight, conv.bias, None)
+                t, _, _ = AG.conv_rows(x, conv, cd)
             else:
                 # channel-last source: columns (i, j, ci) -- the weight viewed in that order (a permute autograd maps back)
                 t = AG.Linear.apply(AG.PatchRowsNHWC.apply(t, B, H, W, ph, pw), conv.weight.permute(0, 2, 3, 1), conv.bias, None)
@@ -286,21 +277,18 @@ class S2MLPv2(E.EngineModule):
             for b2 in blk.model:
                 pre, mlp = b2[0], b2[1]
                 att = pre.fn
-                n = AG.LayerNorm.apply(t, pre.norm.weight, pre.norm.bias, pre.norm.eps)
-                y = AG.Linear.apply(n, att.mlp1.weight, att.mlp1.bias, None)                                 # (rows, 3C)
+                n = AG.layer_norm(t, pre.norm)
+                y = AG.linear(n, att.mlp1)                                                                   # (rows, 3C)
                 x1 = AG.S2Shift.apply(y[:, :C], B, H, W, 1, smear)
                 x2 = AG.S2Shift.apply(y[:, C:2 * C], B, H, W, 2, smear)
                 a = AG.split_attention(x1, x2, y[:, 2 * C:], att.split_attention, B, H * W)
-                t = AG.Linear.apply(a, att.mlp2.weight, att.mlp2.bias, t)
-                n2 = AG.LayerNorm.apply(t, mlp.norm.weight, mlp.norm.bias, mlp.norm.eps)
-                fc1, fc2 = mlp.fn[0], mlp.fn[3]
-                t = AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(n2, fc1.weight, fc1.bias, None)), fc2.weight, fc2.bias, t)
-        head = self.mlp_head[1]
-        logits = AG.Linear.apply(AG.TokenMean.apply(t, B, H * W), head.weight, head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+                t = AG.linear(a, att.mlp2, t)
+                t = AG.mlp(AG.layer_norm(t, mlp.norm), mlp.fn[0], mlp.fn[3], t)
+        logits = AG.linear(AG.TokenMean.apply(t, B, H * W), self.mlp_head[1])
+        return logits.to(x.dtype)
 
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         B = x.shape[0]

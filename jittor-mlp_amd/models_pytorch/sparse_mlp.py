@@ -24,7 +24,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, BlockSequential, Holder, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp, warn_unapplied_dropout
+from .common import Block, BlockSequential, Holder, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp, train_entry
 from .conv_mixer import _bn_affine
 from .utils import pair
 
@@ -353,60 +353,37 @@ class SparseMLP(E.EngineModule):
         PreNormResidual(norm = BatchNorm2d) sublayers); proj_h / proj_w contract over H resp. W: the ViP rearranges with one-channel segments
         (mlpk_norm_apply out_ph / out_pw, mlpk_vip_unpermute) around mlpk_gemm_nt; the concatenation in front of `fuse` = column slices of one
         buffer; the depthwise 3 x 3 = mlpk_dwconv_plain_nhwc (+ adjoint, + mlpk_dwconv_wgrad_nhwc); PatchMerging = mlpk_merge2x2_nhwc."""
-        warn_unapplied_dropout(self)
         from .. import autograd as AG
-        E.require_gpu(x, "SparseMLP.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
-        image_size, patch, cin, num_classes, patcher_norm = self._cfg
+        cd = train_entry(self, x, warn_dropout=True)
+        _, (ph, pw), _, _, patcher_norm = self._cfg
         B, _, H_in, W_in = x.shape
-        ph, pw = patch
         H, W = H_in // ph, W_in // pw
         if (H, W) != self.layers[0].geom[:2]:
             raise ValueError("input size gives a %dx%d grid, the model was built for %dx%d" % ((H, W) + self.layers[0].geom[:2]))
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * H * W, kp), dtype=cd, device=x.device)
-            E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)
-
-        def ln(t, norm):
-            return AG.LayerNorm.apply(t, norm.weight, norm.bias, norm.eps)
-
-        def bn(t, mod):
-            rows, dim = t.shape
-            mean, var = AG.batch_stats(t.detach(), rows, dim)
-            AG.batchnorm_train_affine(mod, mean, var, rows)
-            return AG.BatchNormTrain.apply(t, mod.weight, mod.bias, mean, var, mod.eps)
-
-        conv = self.patcher[0]
-        t = AG.Linear.apply(patches, conv.weight, conv.bias, None)
+        t, _, _ = AG.conv_rows(x, self.patcher[0], cd)
         if patcher_norm:
-            t = ln(t, self.patcher[1][1])
+            t = AG.layer_norm(t, self.patcher[1][1])
         for stage in self.layers:
             C = stage.geom[2]
             for blk in stage.model:
                 dw_pre, mix_pre, mlp = blk[0], blk[1], blk[3]
                 dw = dw_pre.fn[0]
-                t = AG.ScaleAdd.apply(AG.DepthwiseConv.apply(bn(t, dw_pre.norm), dw.weight, dw.bias, B, H, W), t, None)
+                t = AG.ScaleAdd.apply(AG.DepthwiseConv.apply(AG.batch_norm_train(t, dw_pre.norm), dw.weight, dw.bias, B, H, W), t, None)
                 sm = mix_pre.fn[0]
-                n = bn(t, mix_pre.norm)
-                x_h = AG.VipUnpermute.apply(AG.Linear.apply(AG.VipPermute.apply(n, B, H, W, 1, 0), sm.proj_h.weight, sm.proj_h.bias, None), B, H, W, C, 1, 0)
-                x_w = AG.VipUnpermute.apply(AG.Linear.apply(AG.VipPermute.apply(n, B, H, W, 1, 1), sm.proj_w.weight, sm.proj_w.bias, None), B, H, W, C, 1, 1)
-                t = AG.Linear.apply(AG.ConcatCols.apply(x_h, x_w, n), sm.fuse.weight, sm.fuse.bias, t)
-                fc1, fc2 = mlp.fn[0], mlp.fn[3]
-                t = AG.Linear.apply(AG.Gelu.apply(AG.Linear.apply(ln(t, mlp.norm), fc1.weight, fc1.bias, None)), fc2.weight, fc2.bias, t)
+                n = AG.batch_norm_train(t, mix_pre.norm)
+                x_h = AG.VipUnpermute.apply(AG.linear(AG.VipPermute.apply(n, B, H, W, 1, 0), sm.proj_h), B, H, W, C, 1, 0)
+                x_w = AG.VipUnpermute.apply(AG.linear(AG.VipPermute.apply(n, B, H, W, 1, 1), sm.proj_w), B, H, W, C, 1, 1)
+                t = AG.linear(AG.ConcatCols.apply(x_h, x_w, n), sm.fuse, t)
+                t = AG.mlp(AG.layer_norm(t, mlp.norm), mlp.fn[0], mlp.fn[3], t)
             if stage.pooling:
                 pm = stage.patch_merge[1]
-                t = AG.Linear.apply(ln(AG.Merge2x2.apply(t, B, H, W), pm.norm), pm.reduction.weight, None, None)
+                t = AG.linear(AG.layer_norm(AG.Merge2x2.apply(t, B, H, W), pm.norm), pm.reduction)
                 H, W = H // 2, W // 2
-        head_ln, head = self.mlp_head[1], self.mlp_head[3]
-        logits = AG.Linear.apply(AG.TokenMean.apply(ln(t, head_ln), B, H * W), head.weight, head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+        logits = AG.linear(AG.TokenMean.apply(AG.layer_norm(t, self.mlp_head[1]), B, H * W), self.mlp_head[3])
+        return logits.to(x.dtype)
 
     def forward(self, x):
-        if self.training and torch.is_grad_enabled():
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         image_size, patch, cin, num_classes, patcher_norm = self._cfg

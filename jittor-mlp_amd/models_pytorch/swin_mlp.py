@@ -21,7 +21,7 @@ from torch import nn
 
 from .. import _native as N
 from .. import engine as E
-from .common import Block, Holder, LinearMlp, StochasticDepth, TrainDropout, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp
+from .common import Block, Holder, LinearMlp, StochasticDepth, TrainDropout, channel_mlp, finalize_stats, embed_patches, head_linear, layernorm_stats, pack_channel_mlp, train_entry
 
 
 def to_2tuple(v):
@@ -334,30 +334,16 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
         (common.TrainDropout); PatchMerging = mlpk_merge2x2_nhwc."""
         import torch.nn.functional as F
         from .. import autograd as AG
-        E.require_gpu(x, "SwinMLP.forward")
-        if x.dim() != 4:
-            raise ValueError("expected a (B, C, H, W) tensor")
-        cd = self._compute_dtype or x.dtype
-        E.dtype_code(cd)
+        cd = train_entry(self, x)
         pe = self.patch_embed
-        B, cin, H_in, W_in = x.shape
+        B, _, H_in, W_in = x.shape
         assert H_in == pe.img_size[0] and W_in == pe.img_size[1], \
             f"Input image size ({H_in}*{W_in}) doesn't match model ({pe.img_size[0]}*{pe.img_size[1]})."
-        ph, pw = pe.patch_size
-        H, W = H_in // ph, W_in // pw
         dev = x.device
-        kp = E.round_up(cin * ph * pw, 8)              # (mlpk_patchify: ldo % 8 == 0 in every dtype)
-        with E.on_device(x):
-            patches = torch.zeros((B * H * W, kp), dtype=cd, device=dev)
-            E.patchify(x.contiguous(), patches, B, cin, H_in, W_in, ph, pw, 0, kp)
         tables = self.__dict__.setdefault("_tables", {})
-
-        def ln(t, norm):
-            return AG.LayerNorm.apply(t, norm.weight, norm.bias, norm.eps)
-
-        t = AG.Linear.apply(patches, pe.proj.weight, pe.proj.bias, None)
+        t, H, W = AG.conv_rows(x, pe.proj, cd)
         if pe.norm is not None:
-            t = ln(t, pe.norm)
+            t = AG.layer_norm(t, pe.norm)
         if self.ape:
             t = AG.AddPeriodic.apply(t, self.absolute_pos_embed, H * W)
 
@@ -386,7 +372,7 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
                 t_part = AG.position_table(part, H * W, C, dev, tables, ("part", H, W, ws, P_l, P_t, C))
                 t_rev = AG.position_table(rev, Hp * Wp, C, dev, tables, ("rev", H, W, ws, P_l, P_t, C))
                 nwb = B * (Hp // ws) * (Wp // ws)
-                xw = AG.IndexMap.apply(ln(t, blk.norm1), t_part, B, C)                       # (nW*B * ws*ws, C): windows, tokens row-major
+                xw = AG.IndexMap.apply(AG.layer_norm(t, blk.norm1), t_part, B, C)            # (nW*B * ws*ws, C): windows, tokens row-major
                 ch = C // nH
                 heads = []
                 for h in range(nH):
@@ -397,30 +383,22 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
                     heads.append(AG.RowsToTokens.apply(AG.Linear.apply(rows_h, wgt, bias, None), nwb, ws * ws, ch))
                 y = AG.IndexMap.apply(AG.ConcatCols.apply(*heads) if nH > 1 else heads[0], t_rev, B, C)
                 t = AG.drop_add(self, t, y, blk.drop_path_rate if self.training else 0.0, B, H * W)
-                # x + drop_path(drop(fc2(drop(gelu(fc1(norm2(x))))))) (swin_mlp.py:23-30,155)
-                p_mlp = rate(blk.mlp.drop)
-                hdn = AG.dropout(AG.Gelu.apply(AG.Linear.apply(ln(t, blk.norm2), blk.mlp.fc1.weight, blk.mlp.fc1.bias, None)), p_mlp, seed, 1 + 2 * j)
-                if float(blk.drop_path_rate) > 0.0 or p_mlp > 0.0:
-                    z = AG.dropout(AG.Linear.apply(hdn, blk.mlp.fc2.weight, blk.mlp.fc2.bias, None), p_mlp, seed, 2 + 2 * j)
-                    t = AG.drop_add(self, t, z, blk.drop_path_rate, B, H * W)
-                else:
-                    t = AG.Linear.apply(hdn, blk.mlp.fc2.weight, blk.mlp.fc2.bias, t)
+                t = AG.drop_mlp_add(self, t, AG.layer_norm(t, blk.norm2), blk.mlp, blk.drop_path_rate, rate(blk.mlp.drop), seed, 1 + 2 * j, B, H * W)
                 j += 1
             if layer.downsample is not None:
                 ds = layer.downsample
-                t = AG.Linear.apply(ln(AG.Merge2x2.apply(t, B, H, W), ds.norm), ds.reduction.weight, None, None)
+                t = AG.linear(AG.layer_norm(AG.Merge2x2.apply(t, B, H, W), ds.norm), ds.reduction)
                 H, W, C = H // 2, W // 2, 2 * C
-        pooled = AG.TokenMean.apply(ln(t, self.norm), B, H * W)
+        pooled = AG.TokenMean.apply(AG.layer_norm(t, self.norm), B, H * W)
         if not isinstance(self.head, nn.Linear):
-            return pooled if pooled.dtype == x.dtype else pooled.to(x.dtype)
-        logits = AG.Linear.apply(pooled, self.head.weight, self.head.bias, None)
-        return logits if logits.dtype == x.dtype else logits.to(x.dtype)
+            return pooled.to(x.dtype)
+        return AG.linear(pooled, self.head).to(x.dtype)
 
     def _dropout_modules(self):
         return [self.pos_drop] + [blk.mlp.drop for layer in self.layers for blk in layer.blocks]
 
     def forward(self, x):
-        if self.training and (torch.is_grad_enabled() or self._dropout_active()):
+        if self._train_path():
             return self._forward_train(x)
         cd = self._resolve(x)
         pe = self.patch_embed
