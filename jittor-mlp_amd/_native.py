@@ -46,7 +46,6 @@ PROTOTYPES = {
     "mlpk_gemm_nt": (c_int, [ctypes.POINTER(GemmDesc), c_void_p]),
     "mlpk_gemm_nt_pair": (c_int, [ctypes.POINTER(GemmDesc), ctypes.POINTER(GemmDesc), c_void_p]),
     "mlpk_conv_gemm_nhwc_supported": (c_int, [c_int] * 6),
-    "mlpk_merge2x2_row_stats": (c_int, [c_int, c_void_p] + [c_int] * 4 + [c_float, c_void_p, c_void_p, c_void_p]),
     "mlpk_merge2x2_stats_combine": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     "mlpk_conv_gemm_nhwc": (c_int, [ctypes.POINTER(GemmDesc)] + [c_int] * 8 + [c_void_p]),
     "mlpk_gemm_row_parts": (c_int, [ctypes.POINTER(GemmDesc), ctypes.POINTER(c_int)]),
@@ -102,9 +101,6 @@ PROTOTYPES = {
     "mlpk_cycle_shift_ln": (c_int, [c_int] + [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
     "mlpk_as_conv2_supported": (c_int, [c_int] * 5),
     "mlpk_channel_mlp_supported": (c_int, [c_int] * 3),
-    "mlpk_linear_gelu_supported": (c_int, [c_int] * 4),
-    "mlpk_linear_gelu": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
-                                 c_void_p, c_void_p]),
     "mlpk_swin_spatial_supported": (c_int, [c_int] * 4),
     "mlpk_swin_spatial": (c_int, [c_int, c_void_p] + [c_int] * 10 + [c_void_p] * 7),
     "mlpk_channel_mlp": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
@@ -176,7 +172,7 @@ def lib():
         for name, (res, args) in PROTOTYPES.items():
             fn = getattr(handle, name)          # AttributeError if a declared symbol is not exported
             fn.restype, fn.argtypes = res, args
-        if handle.mlpk_abi_version() != 12:
+        if handle.mlpk_abi_version() != 13:
             raise MlpkError("libmlpk.so ABI version mismatch")
         _lib = handle
     return _lib

@@ -22,7 +22,6 @@
 //     one barrier per iteration.
 // LDS (D = 2): 3 x (C / 16) KiB + 4 x (C / 16) KiB + 4 (b1) + 4 (csum) + 1 (b2) KiB = 93 KiB at C = 192.
 #include "mlpk_common.h"
-#include <cstdlib>
 
 namespace mlpk {
 
@@ -38,7 +37,6 @@ struct ChanMlpArgs {
     const void* R;          // (M, ldr) or NULL
     void* out;              // (M, ldo)
     float* row_part;        // optional by-product: (sum, sum of squares) of the C values written to row m at [2 m], [2 m + 1]
-                            // (first product alone: planes of 32 columns, pair of row m in plane g at [2 (g M + m)])
     int M, G, ldx, ldw1, ldw2, ldr, ldo, ln_group;
 };
 
@@ -89,30 +87,25 @@ static __device__ __forceinline__ float cm_load4(const void* ptr) {
 }
 
 constexpr int CM_BM = 256;
-constexpr int CM_HID_MAX = 1024;                          // both products
-constexpr int CM_N_MAX = 4096;                             // the first product alone
+constexpr int CM_HID_MAX = 1024;
 
 // D = how many iterations ahead the weight pieces are requested (an iteration here is 3-6x shorter than the token kernel's: 24-48
-// MFMAs per wave; deeper rings were tried and change nothing, see cm_launch)
-template <int KS1, int NB, int D, bool FC2 = true> struct CmGeo {
-    static constexpr int HMAX = FC2 ? CM_HID_MAX : CM_N_MAX;
+// MFMAs per wave).  Deeper rings (4, 6) changed nothing (profiles/r04_chanmlp_depth_ab.txt): the kernel is bound by the GELU's VALU
+// instructions, not by the weight stream.
+constexpr int D = 2;
+
+template <int KS1, int NB> struct CmGeo {
     static constexpr int N1 = 2 * KS1;                      // W1 pieces per group: plane kk, halves of 16 rows
-    static constexpr int P = N1 + (FC2 ? NB : 0);           // + W2 pieces: 16 output channels each
+    static constexpr int P = N1 + NB;                       // + W2 pieces: 16 output channels each
     static constexpr int PPW = (P + 7) / 8;                 // pieces per wave and iteration (the last ones issued twice)
-    static constexpr int ST1 = N1 * 1024, ST2 = FC2 ? NB * 1024 : 0;
+    static constexpr int ST1 = N1 * 1024, ST2 = NB * 1024;
     static constexpr int R1 = 0, R2 = (D + 1) * ST1;        // W1 ring: D + 1 stages; W2 ring: D + 2 (the late half reads slab t - 1)
     static constexpr int B1 = R2 + (D + 2) * ST2;
-    static constexpr int CS = B1 + HMAX * 4;
-    static constexpr int B2 = CS + HMAX * 4;
+    static constexpr int CS = B1 + CM_HID_MAX * 4;
+    static constexpr int B2 = CS + CM_HID_MAX * 4;
     static constexpr int LDS = B2 + 16 * NB * 4;
 };
 
-// FC2 = false: the FIRST product alone -- out[m, n] = gelu(norm-fold(x[m, :] . W1[n, :]) + b1[n]) for K = 32 KS1 <= 512 and any N = 32 G: the
-// short-K GELU GEMM with its rows resident (gMLP's channel_proj1, the fc1 of the K = 384 channel MLPs).  The one-wave-per-SIMD q4 tile
-// cannot hide a GELU epilogue behind 4-6 k-steps of MFMAs (gMLP proj1: 128 MFMAs against 2300 epilogue instructions per tile); here two
-// waves per SIMD alternate between MFMAs and GELU, and a lane's 8 rounded values -- with W1's ROWS stored as [hidden 8 f + 4 j + r at row
-// 16 j + 4 f + r] of every 32 -- are 8 consecutive output columns: one 16-byte store per (row, group), no epilogue at all.  STATS: the
-// by-product planes of 32 columns in the canonical order (a lane's chunk by chunk_sums, then (c0 + c1) + (c2 + c3) across the 4 lanes).
 // Round 6 (profiles/r06_chanmlp_variants.txt; -DCM_WGS2=0 / -DCM_PREFETCH=0 rebuild the round-5 kernel for A/B):
 //   * the residual rows ARE the operand rows in every pre-norm residual block (R == x): read once (template SAME);
 //   * the next tile's rows are requested straight after the tile's last fc1 -- their registers are free from there on -- and travel
@@ -126,22 +119,20 @@ template <int KS1, int NB, int D, bool FC2 = true> struct CmGeo {
 #define CM_PREFETCH 1
 #endif
 // (f16 at C = 96: its longer GELU polynomial does not fit 128 registers without spilling -- one workgroup per CU there)
-template <typename T, int KS1, int D, bool FC2, bool SAME> struct CmWgs {
-    static constexpr int value = (CM_WGS2 && FC2 && SAME && D == 2 && (KS1 <= 2 || (KS1 == 3 && dtype_of<T>::value == MLPK_BF16))) ? 2 : 1;
+template <typename T, int KS1, bool SAME> struct CmWgs {
+    static constexpr int value = (CM_WGS2 && SAME && (KS1 <= 2 || (KS1 == 3 && dtype_of<T>::value == MLPK_BF16))) ? 2 : 1;
 };
 
 // SAME: the residual rows ARE the operand rows (R == x, the pre-norm residual block of every family): read once
-template <typename T, int KS1, int NB, int D, bool FC2 = true, bool STATS = false, bool SAME = false>
-__global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value)) chan_mlp_kernel(const ChanMlpArgs p) {
-    using Geo = CmGeo<KS1, NB, D, FC2>;
+template <typename T, int KS1, int NB, bool SAME>
+__global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, SAME>::value)) chan_mlp_kernel(const ChanMlpArgs p) {
+    using Geo = CmGeo<KS1, NB>;
     constexpr int PPW = Geo::PPW, N1 = Geo::N1, P = Geo::P;
     constexpr int C = 16 * NB;
-    constexpr int NSTORE = FC2 ? 0 : (STATS ? 4 : 2);       // vector-memory stores a wave issues per iteration (first product alone)
     // the next tile's rows requested straight after the tile's last fc1 (a residual that is not the operand doubles the registers
     // requested ahead: the wide widths would spill)
-    constexpr bool PRE = CM_PREFETCH && FC2 && (SAME || KS1 <= 4);
-    static_assert(!FC2 || NB == 2 * KS1, "C = 32 KS1 = 16 NB");
-    static_assert(FC2 || D == 2, "the store-counting waits below are written for two iterations of look-ahead");
+    constexpr bool PRE = CM_PREFETCH && (SAME || KS1 <= 4);
+    static_assert(NB == 2 * KS1, "C = 32 KS1 = 16 NB");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     const int tid = threadIdx.x;
@@ -205,7 +196,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         int g0 = it;
         g0 = g0 < G ? g0 : g0 - G;
         g0 = g0 < G ? g0 : g0 - G;
-        g0 = g0 < G ? g0 : g0 - G;                          // (G >= 2, D <= 6)
+        g0 = g0 < G ? g0 : g0 - G;                          // (G >= 2)
         piece_bases(g0);
         so1 = (unsigned)it * Geo::ST1;
         so2 = (unsigned)it * Geo::ST2;
@@ -218,10 +209,10 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         b1s[i] = p.b1[i];
         css[i] = fold ? p.csum[i] : 0.f;
     }
-    if (FC2 && tid < C) b2s[tid] = p.b2[tid];
+    if (tid < C) b2s[tid] = p.b2[tid];
     __syncthreads();
 
-    u32x4 xa[2][KS1], rr[2][FC2 && !SAME ? KS1 : 1];
+    u32x4 xa[2][KS1], rr[2][!SAME ? KS1 : 1];
     float lmu[2], lrs[2], nmu[2], nrs[2];
     // RULE for the asm loads: the compiler believes their results are there when they are issued.  So no value they produce may meet
     // another definition of the same variable (a branch merge, a loop back edge: the register copies of such a merge would read the
@@ -235,7 +226,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
             gm = gm < p.M ? gm : p.M - 1;
 #pragma unroll
             for (int kk = 0; kk < KS1; ++kk) xa[i][kk] = cm_load16(x + (size_t)gm * p.ldx + kk * 32 + fg * 8);
-            if constexpr (FC2 && !SAME) {
+            if constexpr (!SAME) {
                 // (no residual: the operand rows once more, zeroed in settle)
                 const T* rsrc = R ? R + (size_t)gm * p.ldr : x + (size_t)gm * p.ldx;
 #pragma unroll
@@ -270,7 +261,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
     // by-product statistics two more, of which the first two stores are then waited for as well; a tile with fewer stores -- rows past M
     // -- is a workgroup's last): everything but those stores.  Then the loaded registers are handed to the compiler.
     auto settle = [&](const bool behind) {
-        constexpr int NS = FC2 ? 2 * KS1 : 0;
+        constexpr int NS = 2 * KS1;
         static_assert(NS <= 15, "vmcnt immediate");
         if (!behind) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NS) : "memory");
@@ -278,7 +269,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         for (int i = 0; i < 2; ++i) {
 #pragma unroll
             for (int kk = 0; kk < KS1; ++kk) asm volatile("" : "+v"(xa[i][kk]));
-            if constexpr (FC2 && !SAME) {
+            if constexpr (!SAME) {
 #pragma unroll
                 for (int kk = 0; kk < KS1; ++kk) {
                     asm volatile("" : "+v"(rr[i][kk]));
@@ -290,7 +281,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         }
     };
 
-    f32x4 acc2[2][FC2 ? NB : 1];
+    f32x4 acc2[2][NB];
     f32x4 a1[2][2];
     auto frag_off = [&](const int ln) {
         const int fr = ln & 15;
@@ -305,7 +296,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
             for (int j = 0; j < 2; ++j) a1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
         // fragment pairs read ahead of their MFMAs, pinned there (two workgroups per CU: 128 registers per wave, and twice the waves
         // to hide a fragment read behind)
-        constexpr int BWD = CmWgs<T, KS1, D, FC2, SAME>::value > 1 ? 2 : (KS1 < 3 ? KS1 : 3);
+        constexpr int BWD = CmWgs<T, KS1, SAME>::value > 1 ? 2 : (KS1 < 3 ? KS1 : 3);
         u32x4 bw[BWD + 1][2];
 #pragma unroll
         for (int kk = 0; kk < BWD; ++kk) {
@@ -347,10 +338,9 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         }
     };
     auto fc2 = [&](const unsigned st4, const int ln) {
-      if constexpr (FC2) {
         const int f_rd = frag_off(ln);
         const char* r2 = smem + Geo::R2 + st4 * Geo::ST2;
-        constexpr int BFD = CmWgs<T, KS1, D, FC2, SAME>::value > 1 ? 3 : (NB < 4 ? NB : 4);                // W2 fragments read ahead of their MFMAs
+        constexpr int BFD = CmWgs<T, KS1, SAME>::value > 1 ? 3 : (NB < 4 ? NB : 4);                // W2 fragments read ahead of their MFMAs
         u32x4 bf[BFD + 1];
 #pragma unroll
         for (int j = 0; j < BFD; ++j) bf[j] = *reinterpret_cast<const u32x4*>(r2 + j * 1024 + f_rd);
@@ -362,26 +352,6 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
             acc2[1][j] = CmMma<T>::run(bf[j % (BFD + 1)], hf[1], acc2[1][j]);
             __builtin_amdgcn_sched_barrier(0);
         }
-      }
-    };
-
-    // first product alone: the rounded hidden of group g IS the output -- 8 consecutive columns per lane
-    auto store_h = [&](const int g, const int tile, const int ln) {
-        const int frow = ln & 15, fg = ln >> 4;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const size_t gm = (size_t)tile * CM_BM + wave * 32 + i * 16 + frow;
-            *reinterpret_cast<u32x4*>(out + gm * p.ldo + g * 32 + fg * 8) = hf[i];
-            if constexpr (STATS) {
-                float ssum = 0.f, ssq = 0.f;
-                chunk_sums<T>(hf[i], ssum, ssq);
-                ssum = cm_rows4_sum(ssum);
-                ssq = cm_rows4_sum(ssq);
-                // (every lane stores: lanes fg != 0 to their own row's pair as well -- the same value four times, one store instruction
-                // with a fixed count for the vmcnt arithmetic)
-                *reinterpret_cast<f32x2*>(p.row_part + ((size_t)g * p.M + gm) * 2) = f32x2{ssum, ssq};
-            }
-        }
     };
 
     auto run = [&](auto lag_c) {
@@ -391,7 +361,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
         for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) { lmu[i] = nmu[i]; lrs[i] = nrs[i]; }
-            if constexpr (FC2) {
+            {
                 // accumulators start from R + b2: lane (row, fg) holds channels 32 q + 8 fg + {0..3} in block 2q, + {4..7} in block 2q + 1
                 const int fg = lane_now() >> 4;
 #pragma unroll
@@ -410,12 +380,11 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
             auto iter = [&](auto first_c, auto second_c, const int t, auto last_c) {
                 constexpr bool LAST = decltype(last_c)::value;
                 constexpr bool FIRST = decltype(first_c)::value;
-                // what may still be in flight at this point: the pieces requested last iteration -- and, first product alone, the stores
-                // of last iteration (none in a tile's iteration 0 for the late half: the sync of iteration 1 does not count them)
-                constexpr int INFLIGHT = (D - 1) * PPW + (decltype(second_c)::value ? 0 : NSTORE);
-                // (both products: the pieces of a tile's first two groups were requested during the previous tile and are covered by the
-                // wait at the top of the tile -- counting here would wait for the previous epilogue's stores, which are younger)
-                if constexpr (FC2 && (FIRST || decltype(second_c)::value)) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                // what may still be in flight at this point: the pieces requested last iteration
+                constexpr int INFLIGHT = (D - 1) * PPW;
+                // (the pieces of a tile's first two groups were requested during the previous tile and are covered by the wait at the top
+                // of the tile -- counting here would wait for the previous epilogue's stores, which are younger)
+                if constexpr (FIRST || decltype(second_c)::value) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(INFLIGHT) : "memory");
                 asm volatile("s_barrier" ::: "memory");
                 int g2 = t + D;                                // pieces of iteration t + D (the next tile's first groups at the end of this one)
@@ -438,12 +407,11 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
                     // the epilogue instead of after them
                     if constexpr (LAST) load_tile(tile + gridDim.x, ln);
                     gelu(t, ln);
-                    if constexpr (FC2) fc2(s4, ln); else store_h(t, tile, ln);
+                    fc2(s4, ln);
                 } else {
                     if constexpr (!FIRST) {
                         gelu(t - 1, ln);
-                        if constexpr (FC2) fc2(s4 == 0 ? D + 1 : s4 - 1, ln);    // slab t - 1: stage (gi - 1) % (D + 2)
-                        else store_h(t - 1, tile, ln);
+                        fc2(s4 == 0 ? D + 1 : s4 - 1, ln);                      // slab t - 1: stage (gi - 1) % (D + 2)
                     }
 #pragma unroll
                     for (int pi = PH; pi < PPW; ++pi) issue(pi, ln);
@@ -462,13 +430,13 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, D, FC2, SAME>::value))
             if constexpr (LAG) {
                 const int ln = lane_now();
                 gelu(G - 1, ln);
-                if constexpr (FC2) fc2(s4 == 0 ? D + 1 : s4 - 1, ln); else store_h(G - 1, tile, ln);
+                fc2(s4 == 0 ? D + 1 : s4 - 1, ln);
             }
             // ---- tile epilogue: one rounding, 16-byte stores straight from the accumulators; then the next tile's rows ----
             const int le = lane_now();
             const int frow = le & 15, fg = le >> 4;
 #pragma unroll
-            for (int i = 0; i < (FC2 ? 2 : 0); ++i) {
+            for (int i = 0; i < 2; ++i) {
                 const int gm = tile * CM_BM + wave * 32 + i * 16 + frow;
                 float ssum = 0.f, ssq = 0.f;
 #pragma unroll
@@ -513,51 +481,17 @@ static int cm_grid_cap() {
     return cap;
 }
 
-template <typename T, int KS1, int D>
-static int cm_launch_d(const ChanMlpArgs& a, hipStream_t s) {
-    using Geo = CmGeo<KS1, 2 * KS1, D>;
+template <typename T, int KS1>
+static int cm_launch(const ChanMlpArgs& a, hipStream_t s) {
+    using Geo = CmGeo<KS1, 2 * KS1>;
     const bool same = a.R == a.x && a.ldr == a.ldx;
-    auto k = same ? chan_mlp_kernel<T, KS1, 2 * KS1, D, true, false, true> : chan_mlp_kernel<T, KS1, 2 * KS1, D, true, false, false>;
+    auto k = same ? chan_mlp_kernel<T, KS1, 2 * KS1, true> : chan_mlp_kernel<T, KS1, 2 * KS1, false>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS);
     if (e != hipSuccess) return MLPK_ESHAPE;
     const int tiles = (a.M + CM_BM - 1) / CM_BM;
-    const int cap = cm_grid_cap() * (same ? CmWgs<T, KS1, D, true, true>::value : 1);
+    const int cap = cm_grid_cap() * (same ? CmWgs<T, KS1, true>::value : 1);
     const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), Geo::LDS, s, a);
-    MLPK_LAUNCH_CHECK();
-    return 0;
-}
-
-template <typename T, int KS1>
-static int cm_launch(const ChanMlpArgs& a, hipStream_t s) {
-    // MLPK_CM_DEPTH = 2 | 4 | 6: A/B aid (6 only while its rings fit the LDS).  Measured (profiles/r04_chanmlp_depth_ab.txt): no
-    // difference -- the kernel is bound by the GELU's VALU instructions (SQ_ACTIVE_INST_VALU 44 % of the time, MFMA busy 20 %), not by
-    // the weight stream -- so the shallow rings of the token kernel stay.
-    static const int want = getenv("MLPK_CM_DEPTH") ? atoi(getenv("MLPK_CM_DEPTH")) : 2;
-    if constexpr (CmGeo<KS1, 2 * KS1, 6>::LDS <= 160 * 1024) {
-        if (want >= 6) return cm_launch_d<T, KS1, 6>(a, s);
-    }
-    if (want >= 4) return cm_launch_d<T, KS1, 4>(a, s);
-    return cm_launch_d<T, KS1, 2>(a, s);
-}
-
-template <typename T, int KS1>
-static int cm_launch_fc1(const ChanMlpArgs& a, hipStream_t s) {
-    using Geo = CmGeo<KS1, 2 * KS1, 2, false>;
-    hipError_t e;
-    const int tiles = a.M / CM_BM;
-    const unsigned grid = (unsigned)(tiles < cm_grid_cap() ? tiles : cm_grid_cap());
-    if (a.row_part) {
-        auto k = chan_mlp_kernel<T, KS1, 2 * KS1, 2, false, true>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), Geo::LDS, s, a);
-    } else {
-        auto k = chan_mlp_kernel<T, KS1, 2 * KS1, 2, false, false>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), Geo::LDS, s, a);
-    }
     MLPK_LAUNCH_CHECK();
     return 0;
 }
@@ -565,35 +499,6 @@ static int cm_launch_fc1(const ChanMlpArgs& a, hipStream_t s) {
 }  // namespace mlpk
 
 using namespace mlpk;
-
-extern "C" int mlpk_linear_gelu_supported(int dtype, int M, int K, int N) {
-    return (dtype == MLPK_F16 || dtype == MLPK_BF16) && M > 0 && M % CM_BM == 0 && (K == 128 || K == 192 || K == 256 || K == 384 || K == 512) && N > 0 &&
-           N % 32 == 0 && N <= CM_N_MAX;
-}
-
-extern "C" int mlpk_linear_gelu(int dtype, const void* x, int ldx, int M, int K, const float* ln_mean, const float* ln_rstd, int ln_group,
-                                const float* csum, const void* w1, int ldw1, const float* b1, int nchunks, void* out, int ldo, float* row_part,
-                                void* stream) {
-    if (!x || !w1 || !b1 || !out) return MLPK_ENULL;
-    if (dtype != MLPK_F16 && dtype != MLPK_BF16) return MLPK_EDTYPE;
-    if (nchunks <= 0 || !mlpk_linear_gelu_supported(dtype, M, K, nchunks * 32)) return MLPK_ESHAPE;
-    if ((ln_mean != nullptr) != (ln_rstd != nullptr) || (ln_mean != nullptr) != (csum != nullptr)) return MLPK_ENULL;
-    if (ln_mean && ln_group <= 0) return MLPK_ESHAPE;
-    if (ldw1 < K || ldw1 % 8 || ldx < K || ldx % 8 || ldo < nchunks * 32 || ldo % 8) return MLPK_ESHAPE;
-    if (((uintptr_t)x & 15) || ((uintptr_t)w1 & 15) || ((uintptr_t)out & 15) || ((uintptr_t)row_part & 7)) return MLPK_EALIGN;
-    ChanMlpArgs a;
-    a.x = x; a.w1 = w1; a.w2 = nullptr; a.b1 = b1; a.csum = csum; a.b2 = nullptr; a.ln_mean = ln_mean; a.ln_rstd = ln_rstd; a.R = nullptr; a.out = out;
-    a.row_part = row_part;
-    a.M = M; a.G = nchunks; a.ldx = ldx; a.ldw1 = ldw1; a.ldw2 = 0; a.ldr = 0; a.ldo = ldo; a.ln_group = ln_mean ? ln_group : 1;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define CM_CASE1(KS1) \
-    case KS1: return dtype == MLPK_BF16 ? cm_launch_fc1<bf16_t, KS1>(a, s) : cm_launch_fc1<f16_t, KS1>(a, s);
-    switch (K / 32) {
-        CM_CASE1(4) CM_CASE1(6) CM_CASE1(8) CM_CASE1(12) CM_CASE1(16)
-        default: return MLPK_ESHAPE;
-    }
-#undef CM_CASE1
-}
 
 extern "C" int mlpk_channel_mlp_supported(int dtype, int C, int hidden) {
     // (hidden >= 96: the kernel peels a tile's last group of 32 hidden units off its steady loop)

@@ -1675,6 +1675,7 @@ static const TileCfg kTiles[] = {
     {256, 128, 2, 2, 4},   // algo 15: "q4" generated kernels (mlpk_gemm_q4.hip): 4 waves = one per SIMD, 144 KiB LDS, epilogue of tile
                            //          T - 1 issued behind the MFMAs of tile T
     {8, 64, 4, 1, 5},      // algo 16: skinny fp32 kernel (mlpk_gemm_skinny.hip): no MFMA, the whole chip on a product of a few hundred MFLOP
+                           // -- only when asked for (ViP's chain): as an automatic choice it was slower (profiles/r04_skinny_ab.txt)
 };
 static const int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
 
@@ -2139,18 +2140,6 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
                         (d->N == 768 && d->K <= 512 && tiles >= 1024);
             if (q4_mode >= 2 || take) algo = 15;
         }
-    }
-    if (algo == 0 && d->dtype == MLPK_F32) {
-        // round 4: the small fp32 products of the SplitAttention / re-weighting MLPs (M = batch rows, K <= 1536) CAN run on the skinny
-        // kernel (algo 16) -- built because the MFMA tiles run them on <= 72 workgroups with a serial K loop (15-24 us each).  Measured
-        // (profiles/r04_skinny_ab.txt): S2-MLPv2 8.76 -> 8.74 ms, CycleMLP-B1 unchanged (these products are launch-latency bound either
-        // way), ViP-S7 30.1 -> 30.6 ms WORSE: its chain runs on a side stream beside a persistent GEMM, and a grid of 1024 small
-        // workgroups sits on every CU the persistent kernel's workgroups (all of a CU's LDS and registers each) are waiting for, where
-        // the 64 x 64 tile's 24-128 workgroups hold up only that many.  So it is opt-in (MLPK_GEMM_SKINNY=1), not the default.  The rule
-        // uses N and K only: which kernel computes a row must not depend on the batch
-        static const bool sk_on = getenv("MLPK_GEMM_SKINNY") && atoi(getenv("MLPK_GEMM_SKINNY")) == 1;
-        SkinnyCall sc;
-        if (sk_on && (long long)d->N * d->K <= (1ll << 21) && d->K <= 2048 && d->M <= 16384 && skinny_call_of(a, d->dtype, trans, sc)) algo = 16;
     }
     if (algo == 0) algo = auto_algo(d->M, d->N, d->K, epc, glds_ok, p8_ok, stats);
     if (algo < 1 || algo > kNumTiles) return MLPK_EMODE;

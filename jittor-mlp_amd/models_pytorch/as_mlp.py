@@ -11,7 +11,6 @@ The axial shift (utils/shift_cuda.py:44-72) runs as mlpk_shift_nhwc; conv2_2's e
 GELU and adds conv2_1's GELU output, conv3's and fc2's epilogues add the residual.
 DropPath is the identity in eval mode (as_mlp.py:144,159-160); `use_checkpoint` is accepted and ignored.
 """
-import os
 
 import torch
 from torch import nn
@@ -21,11 +20,9 @@ from .. import engine as E
 from .common import Block, Holder, StochasticDepth, SubModule, TrainDropout, finalize_stats, head_linear, train_entry, two_layer_mlp
 from .utils.shift import Shift
 
-# GroupNorm(1,C) statistics from the producing GEMMs' epilogues (mlpk.h row_part, per-sample groups).  Off by default: measured
-# SLOWER than the separate statistics pass on AS-MLP-T (the C = 96 / 192 GEMMs are short-K and epilogue-bound, and the statistics
-# pass over a whole sample runs at HBM speed); MLPK_ASMLP_EPILOGUE_STATS=1 switches it on (A/B runs, tests).
-EPILOGUE_STATS = os.environ.get("MLPK_ASMLP_EPILOGUE_STATS", "0") == "1"
-# (round 5: only on the stages whose GEMMs run on the generated tile, C >= 384 -- also slower: 6.52 vs 6.43 ms, profiles/r05_as_conv2_384_ab.txt)
+# The GroupNorm(1,C) statistics of what the GEMMs write come from a statistics pass: taking them from the GEMMs' epilogues (mlpk.h row_part)
+# measured slower on AS-MLP-T -- the C = 96 / 192 GEMMs are short-K and epilogue-bound, and the pass over a whole sample runs at HBM speed
+# (on the C >= 384 stages too: 6.52 vs 6.43 ms, profiles/r05_as_conv2_384_ab.txt).
 
 
 def to_2tuple(v):
@@ -319,7 +316,6 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
         the layer's resolution and width (AxialShiftedBlock called on its own).  Returns (cur, H, W, C, have, mean, rstd)."""
         mean = rstd = None
         have = False          # (mean, rstd) of the current layer already hold the per-sample statistics of `cur`
-        pending = None        # by-product partials of the PatchMerging GEMM that produced `cur`
         for li, layer in enumerate(self.layers):
             if only is not None and li != only[0]:
                 continue
@@ -338,26 +334,22 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
             fused = cd != torch.float32 and C % 8 == 0 and (C + self._shift - 1) // self._shift >= 8
             mean = ws.get(tag + ".mean", (B,), torch.float32)
             rstd = ws.get(tag + ".rstd", (B,), torch.float32)
-            have = finalize_stats(ws, pending, rows, C, tag=tag, group=HW) is not None
-            pending = None
+            have = False
 
-            def stats(t, width, got=None):
-                # per-sample statistics reduced from the per-row pairs of the GEMM that wrote t (mlpk.h row_part) when it delivered
-                # them (EPILOGUE_STATS), else a statistics pass over t
-                if finalize_stats(ws, got, rows, width, tag=tag, group=HW) is None:
-                    E.row_stats(t, B, HW * width, HW * width, mean, rstd)
+            def stats(t):
+                # per-sample statistics: a pass over t
+                E.row_stats(t, B, HW * C, HW * C, mean, rstd)
 
-            part = (ws, "l%d.part" % li) if EPILOGUE_STATS else None
             for bi in range(len(layer.blocks)):
                 if only is not None and only[1] != "layer" and bi != only[1]:
                     continue
                 p = "l%d.b%d." % (li, bi)
                 if fused:
                     if not have:
-                        stats(cur, C)
-                    got = E.gemm(cur, pk[p + "c1f.w"], t1, rows, C, C, bias=pk[p + "c1f.b"], ln=(mean, rstd, pk[p + "c1f.csum"]), ln_group=HW,
-                                 tag="as_conv", part=part)                                           # conv1(norm1(x))
-                    stats(t1, C, got)
+                        stats(cur)
+                    E.gemm(cur, pk[p + "c1f.w"], t1, rows, C, C, bias=pk[p + "c1f.b"], ln=(mean, rstd, pk[p + "c1f.csum"]), ln_group=HW,
+                           tag="as_conv")                                                            # conv1(norm1(x))
+                    stats(t1)
                     if pk.get(p + "c21.b") is not None and pk.get(p + "c22.b") is not None and E.as_conv2_supported(cd, H, W, C, self._shift):
                         # round 4 (stages with C = 96 / 192): GroupNorm + GELU, both axial shifts, conv2_1, conv2_2, their GELUs and the sum
                         # in ONE kernel -- the shifts are LDS read addresses of the matrix-core operands (mlpk_as_conv2); bit-equal to the
@@ -366,27 +358,25 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                         st2 = E.as_conv2(t1, t0, B, H, W, C, self._shift, mean, rstd, pk[p + "an1.g"], pk[p + "an1.b"],
                                          pk[p + "c21.w"], pk[p + "c21.b"], pk[p + "c22.w"], pk[p + "c22.b"], stats=(ws, tag + ".asc"))
                         t0, t1 = t1, t0                                                              # the sum now lives in what was t0
-                        got = None
                     else:
                         st2 = None
                         E.norm_shift_nhwc(t1, t0, t2, B, H, W, C, self._shift, mean, rstd, pk[p + "an1.g"], pk[p + "an1.b"], N.ACT_GELU)
                         E.gemm(t0, pk[p + "c21.w"], t1, rows, C, C, bias=pk[p + "c21.b"], act=N.ACT_GELU, tag="as_conv")      # x_lr (W shift)
-                        got = E.gemm(t2, pk[p + "c22.w"], t1, rows, C, C, bias=pk[p + "c22.b"], act=N.ACT_GELU, R=t1, res=N.RES_ADD,
-                                     tag="as_conv", part=part)                                       # gelu(.) + x_lr (H shift)
-                    if st2 is None:
-                        stats(t1, C, got)
+                        E.gemm(t2, pk[p + "c22.w"], t1, rows, C, C, bias=pk[p + "c22.b"], act=N.ACT_GELU, R=t1, res=N.RES_ADD,
+                               tag="as_conv")                                                        # gelu(.) + x_lr (H shift)
+                        stats(t1)
                         st2 = (mean, rstd)
                     dp1 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)  # train mode: x + drop_path(.) (as_mlp.py:159)
-                    got = E.gemm(t1, pk[p + "c3f.w"], cur, rows, C, C, bias=pk[p + "c3f.b"], ln=(st2[0], st2[1], pk[p + "c3f.csum"]), ln_group=HW,
-                                 R=cur, res=N.RES_ADD, tag="as_conv", part=part if dp1 is None else None,
-                                 rscale=dp1, rperiod=rows if dp1 is not None else 0)                 # x + conv3(norm2(.))
-                    stats(cur, C, got)
+                    E.gemm(t1, pk[p + "c3f.w"], cur, rows, C, C, bias=pk[p + "c3f.b"], ln=(st2[0], st2[1], pk[p + "c3f.csum"]), ln_group=HW,
+                           R=cur, res=N.RES_ADD, tag="as_conv", rscale=dp1, rperiod=rows if dp1 is not None else 0)  # x + conv3(norm2(.))
+                    stats(cur)
                     dp2 = self._drop_scale(layer.blocks[bi].drop_path_rate, B, HW, cd, cur.device)  # ... x + drop_path(mlp(norm2(x))) (:160)
                     if dp2 is not None:
                         E.gemm(cur, pk[p + "fc1f.w"], hbuf, rows, hid, C, bias=pk[p + "fc1f.b"], act=N.ACT_GELU,
                                ln=(mean, rstd, pk[p + "fc1f.csum"]), ln_group=HW, tag="as_fc1")
-                        got = E.gemm(hbuf, pk[p + "fc2.w"], cur, rows, C, hid, bias=pk[p + "fc2.b"], R=cur, res=N.RES_ADD, tag="as_fc2",
-                                     rscale=dp2, rperiod=rows)
+                        E.gemm(hbuf, pk[p + "fc2.w"], cur, rows, C, hid, bias=pk[p + "fc2.b"], R=cur, res=N.RES_ADD, tag="as_fc2",
+                               rscale=dp2, rperiod=rows)
+                        got = None
                     elif (p + "mlpf") in pk and E.channel_mlp_fused_supported(cd, C, hid):
                         # (its by-product statistics are one plane, summed inside a wave: always taken -- unlike the s3 tile's, whose
                         # statistics epilogue costs more than the pass it saves, profiles/r04_epilogue_stats_ab.txt)
@@ -395,7 +385,8 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                     else:
                         E.gemm(cur, pk[p + "fc1f.w"], hbuf, rows, hid, C, bias=pk[p + "fc1f.b"], act=N.ACT_GELU,
                                ln=(mean, rstd, pk[p + "fc1f.csum"]), ln_group=HW, tag="as_fc1")
-                        got = E.gemm(hbuf, pk[p + "fc2.w"], cur, rows, C, hid, bias=pk[p + "fc2.b"], R=cur, res=N.RES_ADD, tag="as_fc2", part=part)
+                        E.gemm(hbuf, pk[p + "fc2.w"], cur, rows, C, hid, bias=pk[p + "fc2.b"], R=cur, res=N.RES_ADD, tag="as_fc2")
+                        got = None
                     # (mean, rstd) then describe `cur`: the next block's norm1, the PatchMerging norm (a permutation of the same
                     # elements per sample, as_mlp.py:207-213) or the final norm start from them
                     have = finalize_stats(ws, got, rows, C, tag=tag, group=HW) is not None
@@ -433,8 +424,8 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                         mm = ws.get("l%d.gnm.mean" % li, (B,), torch.float32)
                         mr = ws.get("l%d.gnm.rstd" % li, (B,), torch.float32)
                         E.row_stats(cur, B, H * W * C, H * W * C, mm, mr)
-                    pending = E.conv_gemm_nhwc(cur, pk[p + "f.wc"], nxt, B, H, W, C, 2, 2, 2, 0, bias=pk[p + "f.b"], ln=(mm, mr, pk[p + "f.csum"]),
-                                               ln_group=H2 * W2, tag="as_merge", part=(ws, "l%d.mpart" % li) if EPILOGUE_STATS else None)
+                    E.conv_gemm_nhwc(cur, pk[p + "f.wc"], nxt, B, H, W, C, 2, 2, 2, 0, bias=pk[p + "f.b"], ln=(mm, mr, pk[p + "f.csum"]),
+                                     ln_group=H2 * W2, tag="as_merge")
                     cur, H, W, C = nxt, H2, W2, 2 * C
                     continue
                 merged = ws.get("l%d.merged" % li, (B * H2 * W2, 4 * C))
@@ -448,8 +439,8 @@ class AS_MLP(StochasticDepth, TrainDropout, E.EngineModule):
                         mm = ws.get("l%d.gnm.mean" % li, (B,), torch.float32)
                         mr = ws.get("l%d.gnm.rstd" % li, (B,), torch.float32)
                         E.row_stats(merged, B, H2 * W2 * 4 * C, H2 * W2 * 4 * C, mm, mr)
-                    pending = E.gemm(merged, pk[p + "f.w"], nxt, B * H2 * W2, 2 * C, 4 * C, bias=pk[p + "f.b"], ln=(mm, mr, pk[p + "f.csum"]),
-                                     ln_group=H2 * W2, tag="as_merge", part=(ws, "l%d.mpart" % li) if EPILOGUE_STATS else None)
+                    E.gemm(merged, pk[p + "f.w"], nxt, B * H2 * W2, 2 * C, 4 * C, bias=pk[p + "f.b"], ln=(mm, mr, pk[p + "f.csum"]),
+                           ln_group=H2 * W2, tag="as_merge")
                 else:
                     self._gn(ws, "l%d.gnm" % li, merged, B, H2 * W2, 4 * C, pk[p + "g"], pk[p + "b"], merged)
                     E.gemm(merged, pk[p + "w"], nxt, B * H2 * W2, 2 * C, 4 * C, tag="as_merge")

@@ -8,7 +8,6 @@ copy); the spatial GEMM's epilogue adds the per-token bias, multiplies by u (rea
 and stores through the per-image transpose; proj2 GEMM adds bias + residual.
 """
 import contextlib
-import os
 
 import torch
 from torch import nn
@@ -64,10 +63,6 @@ class gMLPBlock(Block):
         self.sgu = SpatialGatingUnit(d_ffn, seq_len)
 
 
-# tuning: how channel_proj1 delivers the SGU LayerNorm's statistics -- "split" (u | v halves, the v half with by-product statistics),
-# "full" (one launch, statistics of all columns), "rowstats" (a statistics pass over the v half)
-P1_MODE = os.environ.get("MLPK_GMLP_P1", "full")      # measured (profiles/r04_gmlp_p1_ab.txt): full 10.23 ms, rowstats 10.85, split 10.96-11.16
-
 
 class gMLP(E.EngineModule):
     """Backbone on tokens (g_mlp.py:41-49)."""
@@ -84,10 +79,6 @@ class gMLP(E.EngineModule):
             # block LayerNorm folded into channel_proj1 (gamma -> weights, beta -> bias, stats in the epilogue)
             pk[p + "p1.w"], pk[p + "p1.b"], pk[p + "p1.csum"] = E.pack_ln_folded(
                 blk.channel_proj1.weight, blk.channel_proj1.bias, blk.norm.weight, blk.norm.bias, dtype, device)
-            w1 = blk.channel_proj1.weight
-            if E.linear_gelu_enabled() and w1.shape[1] in (128, 192, 256, 384, 512) and w1.shape[0] % 32 == 0 and dtype in (torch.float16, torch.bfloat16):
-                # round 4: channel_proj1 + GELU with its rows resident in registers (mlpk_linear_gelu), statistics planes included
-                pk[p + "p1.rr"] = E.pack_linear_gelu(w1, blk.channel_proj1.bias, dtype, device, blk.norm.weight, blk.norm.bias)
             pk[p + "p2.w"] = E.pack_matrix(blk.channel_proj2.weight, dtype, device)
             pk[p + "p2.b"] = E.f32(blk.channel_proj2.bias, device)
             pk[p + "sgu.g"], pk[p + "sgu.b"] = E.f32(blk.sgu.norm.weight, device), E.f32(blk.sgu.norm.bias, device)
@@ -119,25 +110,14 @@ class gMLP(E.EngineModule):
                 # round 4: the SGU LayerNorm (g_mlp.py:19) is the spatial product's operand loader: ONE kernel reads v, normalises,
                 # transposes through LDS, multiplies, gates with u and stores -- the token-transposed tensor and the normalise-and-
                 # transpose pass (17 % of gMLP-S at 256 images) are gone.  Its row statistics come out of channel_proj1's epilogue:
-                # the product is issued as its two halves (u | v, g_mlp.py:18), the v half with the by-product statistics of what it
-                # stores (mlpk.h row_part; a statistics pass over v when the tile cannot deliver them)
-                w1, b1, cs1 = pk[p + "p1.w"], pk[p + "p1.b"], pk[p + "p1.csum"]
+                # one launch with the by-product statistics of all 2F columns (mlpk.h row_part), of which the planes of the v half
+                # (g_mlp.py:18) are the second half of the buffer; a statistics pass over v when the tile cannot deliver them.  (Two
+                # launches u | v, or a statistics pass, measured slower: profiles/r04_gmlp_p1_ab.txt.)
+                got = E.gemm(x, pk[p + "p1.w"], h, rows, 2 * F, C, bias=pk[p + "p1.b"], act=N.ACT_GELU, ln=(mean, rstd, pk[p + "p1.csum"]),
+                             tag="gmlp_proj1", part=(ws, "p1.part"))
                 vst = None
-                if P1_MODE == "split":
-                    E.gemm(x, w1[:F], h, rows, F, C, ldc=2 * F, bias=b1[:F], act=N.ACT_GELU, ln=(mean, rstd, cs1[:F]), tag="gmlp_proj1")
-                    got = E.gemm(x, w1[F:], v, rows, F, C, ldc=2 * F, bias=b1[F:], act=N.ACT_GELU, ln=(mean, rstd, cs1[F:]), tag="gmlp_proj1",
-                                 part=(ws, "p1.part"))
-                    vst = finalize_stats(ws, got, rows, F, tag="v")
-                elif P1_MODE == "full":
-                    # one launch with the statistics of all 2F columns; the planes of the v half are the second half of the buffer
-                    if (p + "p1.rr") in pk and E.linear_gelu_supported(x.dtype, rows, C, 2 * F):
-                        got = E.linear_gelu(x, rows, C, pk[p + "p1.rr"], h, ln=(mean, rstd), part=(ws, "p1.part"))
-                    else:
-                        got = E.gemm(x, w1, h, rows, 2 * F, C, bias=b1, act=N.ACT_GELU, ln=(mean, rstd, cs1), tag="gmlp_proj1", part=(ws, "p1.part"))
-                    if got is not None:
-                        vst = finalize_stats(ws, (got[0][got[1] // 2:], got[1] // 2), rows, F, tag="v")
-                else:
-                    E.gemm(x, w1, h, rows, 2 * F, C, bias=b1, act=N.ACT_GELU, ln=(mean, rstd, cs1), tag="gmlp_proj1")
+                if got is not None:
+                    vst = finalize_stats(ws, (got[0][got[1] // 2:], got[1] // 2), rows, F, tag="v")
                 if vst is None:
                     vst = (ws.get("v.mean", (rows,), torch.float32), ws.get("v.rstd", (rows,), torch.float32))
                     E.row_stats(v, rows, F, 2 * F, vst[0], vst[1])

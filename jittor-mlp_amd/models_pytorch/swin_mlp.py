@@ -264,18 +264,14 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
         nxt = ws_.get("l%d.x" % (li + 1), (B * H2 * W2, 2 * C))
         # round 6: no merged tensor where the last block's GEMM delivered the per-pixel statistics of `cur` (st): the merged rows' LayerNorm statistics are
         # combined from them (mlpk_merge2x2_stats_combine: 1.6 MB instead of a pass over the activations) and the reduction reads `cur` through the 2 x 2
-        # window (mlpk_conv_gemm_nhwc, the weight's column blocks in its tap order).  Without st: MLPK_MERGE_IMPLICIT=1 takes the statistics from a pass
-        # over the windows (mlpk_merge2x2_row_stats: measured neutral), the default is the gather.
-        implicit = (p + "wc") in pk and pk[p + "w"].shape[1] == 4 * C and E.conv_gemm_nhwc_supported(cur.dtype, C, 2, 2, 2, 0) and \
-            os.environ.get("MLPK_CONV_GEMM", "1") != "0" and (st is not None or os.environ.get("MLPK_MERGE_IMPLICIT") == "1")
+        # window (mlpk_conv_gemm_nhwc, the weight's column blocks in its tap order).  Without st: the gather (a statistics pass over the windows instead
+        # measured neutral, profiles/r06_conv_gemm_ab.txt).
+        implicit = st is not None and (p + "wc") in pk and pk[p + "w"].shape[1] == 4 * C and E.conv_gemm_nhwc_supported(cur.dtype, C, 2, 2, 2, 0) and \
+            os.environ.get("MLPK_CONV_GEMM", "1") != "0"
         if implicit:
             mean = ws_.get("l%d.merge.ln.mean" % li, (B * H2 * W2,), torch.float32)
             rstd = ws_.get("l%d.merge.ln.rstd" % li, (B * H2 * W2,), torch.float32)
-            eps_m = self.layers[li].downsample.norm.eps
-            if st is not None:
-                E.merge2x2_stats_combine(st[0], st[1], B, H, W, mean, rstd, eps_in=1e-5, eps_out=eps_m)
-            else:
-                E.merge2x2_row_stats(cur, B, H, W, C, mean, rstd, eps=eps_m)
+            E.merge2x2_stats_combine(st[0], st[1], B, H, W, mean, rstd, eps_in=1e-5, eps_out=self.layers[li].downsample.norm.eps)
             got = E.conv_gemm_nhwc(cur, pk[p + "wc"], nxt, B, H, W, C, 2, 2, 2, 0, bias=pk[p + "b"], ln=(mean, rstd, pk[p + "csum"]), tag="swin_merge",
                                    part=(ws_, "l%d.merge.part" % li))
         else:

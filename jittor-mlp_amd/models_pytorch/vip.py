@@ -12,7 +12,6 @@ three NT GEMMs; the inverse rearranges; split attention as reduce -> two tiny fp
 softmax -> weighted apply; projection GEMM with the residual in its epilogue.
 """
 import contextlib
-import os
 import torch
 from torch import nn
 
@@ -261,7 +260,7 @@ class _PermutatorBase(E.EngineModule):
                 # in line, 28.8 - 29.6 for the two-kernel branches (profiles/r05_vip_branch_ab.txt)
                 inline = branch and B * G <= 16384 and (ldh + ldw) % 16 == 0 and (G * 2 * seg) % 16 == 0 and C % 16 == 0     # what algo 16 takes
                 sk = dict(algo=16) if inline else {}
-                side = not inline or os.environ.get("MLPK_VIP_CHAIN_SIDE") == "1"      # experiment: the skinny chain BESIDE the channel-branch GEMM
+                side = not inline
                 chain = E.SideChain(ws, "sa", x.device) if side else contextlib.nullcontext()
                 with chain:
                     E.gemm(asum, pk[p + "sa.w1"], o, B * G, 2 * seg, ldh + ldw, bias=pk[p + "sa.b1"], **sk)

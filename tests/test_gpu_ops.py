@@ -1049,7 +1049,7 @@ def test_gemm_skinny_fp32_kernel():
             E.gemm(A[:k].contiguous(), B, Ch, k, Nn, K, bias=bias, act=act, algo=16)
             torch.cuda.synchronize()
             assert torch.equal(Ch, outs[16][:k]), ci                       # same rows, half the batch: same bits
-    # opt-in (MLPK_GEMM_SKINNY=1): measured neutral on its own and worse beside a persistent GEMM (mlpk_gemm.hip, gemm_prepare)
+    # only when asked for: as an automatic choice it was neutral on its own and worse beside a persistent GEMM (mlpk_gemm.hip, kTiles)
     assert ctypes_name(pkg, 256, 384, 768) != "gemm_skinny_f32_kernel"
     with pytest.raises(RuntimeError):
         E.gemm(A, B, C, M, Nn, K, algo=16, R=C, res=N.RES_ADD)               # no residual class
@@ -1419,9 +1419,9 @@ def test_conv_gemm_nhwc_is_im2col_plus_gemm(dtype):
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-def test_patch_merging_without_the_merged_tensor(dtype):
-    """PatchMerging (swin_mlp.py:193-212; sparse_mlp.py:33-50) without the concatenated tensor: mlpk_merge2x2_row_stats gives the LayerNorm statistics of the
-    4 C-wide rows, mlpk_conv_gemm_nhwc multiplies through the 2 x 2 window with the weight's column blocks in tap order (engine.merge_taps) and the LayerNorm
+def test_patch_merging_from_combined_statistics_without_the_merged_tensor(dtype):
+    """PatchMerging (swin_mlp.py:193-212) without the concatenated tensor: mlpk_merge2x2_stats_combine gives the LayerNorm statistics of the 4 C-wide
+    rows from the per-pixel LayerNorm statistics a producer delivered, mlpk_conv_gemm_nhwc multiplies through the 2 x 2 window with the weight's column blocks in tap order (engine.merge_taps) and the LayerNorm
     folded in -- against the reference's own lines (strided slices, cat, LayerNorm, Linear) in fp64 on the rounded operands."""
     pkg = load_pkg()
     E = pkg.engine
@@ -1431,23 +1431,17 @@ def test_patch_merging_without_the_merged_tensor(dtype):
         wlin = rnd((2 * C, 4 * C), torch.float32, 2010 + ci, 1.0 / math.sqrt(4 * C))
         gamma, beta = rnd((4 * C,), torch.float32, 2020 + ci) * 0.3 + 1.0, rnd((4 * C,), torch.float32, 2030 + ci) * 0.2
         rows = B * (H // 2) * (W // 2)
-        mean = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev()); rstd = torch.full_like(mean, float("nan"))
         xg = x.reshape(B * H * W, C).to(dev())
-        E.merge2x2_row_stats(xg, B, H, W, C, mean, rstd, eps=1e-5)
+        pm = torch.empty((B * H * W,), dtype=torch.float32, device=dev()); pr = torch.empty_like(pm)
+        E.row_stats(xg, B * H * W, C, C, pm, pr, eps=1e-5)
+        mean = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev()); rstd = torch.full_like(mean, float("nan"))
+        E.merge2x2_stats_combine(pm, pr, B, H, W, mean, rstd, eps_in=1e-5, eps_out=1e-5)
         xd = x.double()
         cat = torch.cat([xd[:, 0::2, 0::2], xd[:, 1::2, 0::2], xd[:, 0::2, 1::2], xd[:, 1::2, 1::2]], -1).reshape(rows, 4 * C)      # swin_mlp.py:203-208
         torch.cuda.synchronize()
         assert (mean.cpu().double() - cat.mean(1)).abs().max().item() < 1e-5 * max(1.0, cat.abs().max().item()), (str(dtype), ci)
         want_r = 1.0 / torch.sqrt(cat.var(1, unbiased=False) + 1e-5)
         assert ((rstd.cpu().double() - want_r).abs() / want_r).max().item() < 1e-4, (str(dtype), ci)
-        # ... and the same statistics combined from the per-pixel LayerNorm statistics a producer delivered (mlpk_merge2x2_stats_combine)
-        pm = torch.empty((B * H * W,), dtype=torch.float32, device=dev()); pr = torch.empty_like(pm)
-        E.row_stats(xg, B * H * W, C, C, pm, pr, eps=1e-5)
-        m2 = torch.full((rows,), float("nan"), dtype=torch.float32, device=dev()); r2 = torch.full_like(m2, float("nan"))
-        E.merge2x2_stats_combine(pm, pr, B, H, W, m2, r2, eps_in=1e-5, eps_out=1e-5)
-        torch.cuda.synchronize()
-        assert (m2 - mean).abs().max().item() < 1e-5 * max(1.0, cat.abs().max().item()), (str(dtype), ci)
-        assert ((r2 - rstd).abs() / rstd).max().item() < 1e-4, (str(dtype), ci)
         wp, bp, csum = E.pack_ln_folded(wlin, None, gamma, beta, dtype, dev())
         out = torch.full((rows, 2 * C), float("nan"), dtype=dtype, device=dev())
         E.conv_gemm_nhwc(xg, E.merge_taps(wp, C), out, B, H, W, C, 2, 2, 2, 0, bias=bp, ln=(mean, rstd, csum))
@@ -2015,76 +2009,6 @@ def test_swin_spatial_mlp_half_of_a_block_in_one_kernel(dtype):
         want_r = 1.0 / torch.sqrt(gd.var(1, unbiased=False) + 1e-5)
         assert ((r2.cpu().double() - want_r).abs() / want_r).max().item() < 1e-4, (str(dtype), ci)
     assert not E.swin_spatial_supported(dtype, 96, 4, 7) and not E.swin_spatial_supported(dtype, 96, 3, 9) and not E.swin_spatial_supported(torch.float32, 96, 3, 7)
-
-
-@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-def test_short_k_linear_gelu_with_resident_rows(dtype):
-    """mlpk_linear_gelu (round 4): out = gelu(norm(x) W^T + b) for K <= 512 with the rows resident in registers and no epilogue -- gMLP's
-    channel_proj1 (g_mlp.py:28,35) and the fc1 of the K = 384 channel MLPs.  Against fp64 on the rounded operands, against mlpk_gemm_nt with
-    the same fold, and the by-product statistics planes (32 columns each, canonical order) against the sums of what was stored -- and
-    bit-equal to the planes mlpk_gemm_nt delivers for the same output where it delivers them."""
-    pkg = load_pkg()
-    E, N = pkg.engine, pkg._native
-    os.environ["MLPK_LINEAR_GELU"] = "1"                                         # (opt-in: the GEMM tiles are faster on the models' shapes)
-    for ci, (M, K, Nn, norm) in enumerate([(256, 256, 1536, "ln"), (512, 384, 1152, "ln"), (768, 128, 96, None), (256 * 5, 192, 768, "gn"), (256, 512, 2048, "ln"),
-                                            (256 * 270, 256, 512, "ln"), (1024, 384, 1536, None)]):
-        assert E.linear_gelu_supported(dtype, M, K, Nn)
-        w = rnd((Nn, K), torch.float32, 5100 + ci, 1.0 / math.sqrt(K))
-        b = rnd((Nn,), torch.float32, 5110 + ci, 0.3)
-        gamma = rnd((K,), torch.float32, 5120 + ci) * 0.3 + 1.0
-        beta = rnd((K,), torch.float32, 5130 + ci) * 0.2
-        x = (rnd((M, K), dtype, 5140 + ci) * 1.5 + 0.25).to(dev())
-        group, ln = 1, None
-        if norm:
-            group = 1 if norm == "ln" else 128
-            ns = M // group
-            mean = torch.empty((ns,), dtype=torch.float32, device=dev())
-            rstd = torch.empty((ns,), dtype=torch.float32, device=dev())
-            if norm == "ln":
-                E.row_stats(x, M, K, K, mean, rstd)
-            else:
-                xs = x.float().view(ns, -1)
-                mean.copy_(xs.mean(1))
-                rstd.copy_(1.0 / torch.sqrt(xs.var(1, unbiased=False) + 1e-5))
-            ln = (mean, rstd)
-        pack = E.pack_linear_gelu(w, b, dtype, dev(), gamma if norm else None, beta if norm else None)
-        out = torch.full((M, Nn), float("nan"), dtype=dtype, device=dev())
-        ws = E.Workspace(dev(), dtype)
-        got_part = E.linear_gelu(x, M, K, pack, out, ln=ln, ln_group=group, part=(ws, "lg.part"))
-        torch.cuda.synchronize()
-        wf = (w * gamma.view(1, -1) if norm else w).to(dtype).double()
-        bf = (b + w @ beta if norm else b).double()
-        acc = x.cpu().double() @ wf.t()
-        if norm:
-            idx = torch.arange(M) // group
-            acc = (acc - mean.cpu().double()[idx][:, None] * wf.sum(1)[None, :]) * rstd.cpu().double()[idx][:, None]
-        ref = oracle.gelu(acc + bf[None, :])
-        g = out.cpu().double()
-        assert torch.isfinite(g).all(), (str(dtype), ci)
-        scale = max(1.0, ref.abs().max().item())
-        err = (g - ref).abs().max().item()
-        assert err < EPS[dtype] * 4 * scale, (str(dtype), ci, (M, K, Nn), err)
-        # statistics planes: sums over each group of 32 stored columns
-        assert got_part is not None and got_part[1] == Nn // 32 and tuple(got_part[0].shape) == (Nn // 32, M, 2)
-        planes = got_part[0].cpu().double()
-        gs = g.view(M, Nn // 32, 32)
-        assert (planes[:, :, 0].t() - gs.sum(2)).abs().max().item() < 1e-4 * max(1.0, gs.abs().sum(2).max().item())
-        assert (planes[:, :, 1].t() - (gs * gs).sum(2)).abs().max().item() < 1e-4 * max(1.0, (gs * gs).sum(2).max().item())
-        # the GEMM tiles on the same fold
-        if norm:
-            wq, bq, csum = E.pack_ln_folded(w, b, gamma, beta, dtype, dev())
-        else:
-            wq, bq, csum = E.pack_matrix(w, dtype, dev()), b.to(dev()), None
-        two = torch.empty((M, Nn), dtype=dtype, device=dev())
-        gp = E.gemm(x, wq, two, M, Nn, K, bias=bq, act=N.ACT_GELU, ln=(mean, rstd, csum) if norm else None, ln_group=group, part=(ws, "gemm.part"))
-        torch.cuda.synchronize()
-        d2 = (g - two.cpu().double()).abs().max().item()
-        assert d2 < EPS[dtype] * 4 * scale, (str(dtype), ci, d2)
-        if gp is not None and torch.equal(out.view(torch.int16), two.view(torch.int16)):
-            assert gp[1] == got_part[1] and torch.equal(gp[0], got_part[0]), (str(dtype), ci, "planes of equal outputs differ")
-    assert not E.linear_gelu_supported(dtype, 250, 256, 512) and not E.linear_gelu_supported(dtype, 256, 320, 512) and not E.linear_gelu_supported(dtype, 256, 256, 8192)
-    del os.environ["MLPK_LINEAR_GELU"]
-    assert not E.linear_gelu_supported(dtype, 256, 256, 512)
 
 
 @pytest.mark.gpu

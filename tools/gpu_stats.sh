@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of the by-product row statistics (GEMM / token-kernel epilogue -> mlpk_stats_finalize_planar) against the separate
-# mlpk_row_stats pass (MLPK_NO_EPILOGUE_STATS=1), of the side-stream chains of ViP / Hire-MLP (MLPK_NO_SIDE_STREAM=1 = one stream), and of
-# AS-MLP's opt-in per-sample variant.  Every step under its own timeout.
+# mlpk_row_stats pass (MLPK_NO_EPILOGUE_STATS=1), and of the side-stream chains of ViP / Hire-MLP (MLPK_NO_SIDE_STREAM=1 = one stream).
+# Every step under its own timeout.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 run() {   # run <model> <env assignment> <label>
@@ -16,7 +16,3 @@ for m in vip_s7 hiremlp_s; do
   run $m MLPK_NO_SIDE_STREAM=1 "one stream"
   run $m MLPK_NO_SIDE_STREAM=0 "independent chain on side stream"
 done
-run asmlp_t MLPK_ASMLP_EPILOGUE_STATS=0 "separate statistics pass"
-run asmlp_t MLPK_ASMLP_EPILOGUE_STATS=1 "statistics from epilogues"
-echo "asmlp model tests with MLPK_ASMLP_EPILOGUE_STATS=1:"
-MLPK_ASMLP_EPILOGUE_STATS=1 timeout 200 python -m pytest tests/test_gpu_models.py -q -k "asmlp" < /dev/null 2>&1 | tail -1
