@@ -86,6 +86,11 @@ extern "C" {
 
 /* ABI version; bumped on any signature change or removed entry point. */
 int mlpk_abi_version(void);
+/* Test hooks.  The library reads the process environment in exactly four places, each on every call, so that tests/test_gpu_ops.py
+ * can hold a shipping kernel bit-equal to its twin: MLPK_P8_PAIR=0 (mlpk_gemm_nt: the panels of a persistent-tile plan in one launch
+ * per height), MLPK_T4_SHAPE=0 (mlpk_token_mlp layouts 2 / 3: the generic kernel instead of the shaped one), MLPK_MIXSHIFT_TILE=0
+ * (mlpk_mixshift_nhwc: the per-chunk band kernel instead of the tiled one), MLPK_SWIN_SPATIAL_Q=0 (mlpk_swin_spatial: the round-4
+ * kernel).  Results are bit-identical either way; unset, the shipping kernel runs. */
 /* Human-readable message for a return code (static storage). */
 const char* mlpk_strerror(int code);
 
@@ -142,9 +147,16 @@ typedef struct mlpk_gemm_desc {
     int32_t algo;         /* 0 auto; otherwise a tile-config id, see mlpk_gemm_algo_count */
     int32_t ln_group;     /* rows that share one folded statistic: 0 / 1 = LayerNorm (one per row); H*W = GroupNorm(1, C) on channel-last
                              rows (one per sample, as_mlp.py:343-344) */
-    int32_t reserved;     /* 0.  Tuning bits of the persistent tile (A/B runs only; results are bit-identical with every
-                             combination): 16 = 256-row tiles only (no mixed tile heights), 64 = LDS-staged epilogue,
-                             128 = a single column group */
+    int32_t reserved;     /* 0.  Tuning bits (A/B runs and tests only); bits 8 and up are ignored.  Results are bit-identical with
+                             every combination of 16, 32, 64 and 128:
+                               16 = persistent tile (algo 14): 256-row tiles only (no mixed tile heights)
+                               32 = persistent tile: non-temporal stores in the direct epilogue
+                               64 = persistent tile: LDS-staged epilogue
+                              128 = persistent tile and generated tile (algo 15): a single column group
+                             Measurement bits of the hand-written tiles (algo 1 .. 14), results WRONG by construction:
+                                1 = no main loop, 2 = no stores, 4 = no epilogue (in the tiles that implement them),
+                                8 = per-workgroup cycle stamps into R (register-staged and s3 tiles); in -DMLPK_P8_PROF builds
+                                    also the persistent tile's per-workgroup cycle sums into `workspace` */
     /* Unused since ABI 5 (mlpk_gemm_workspace_bytes() == 0): every tile is computed by one workgroup, in one K order,
        so results never depend on the batch a row is computed in.  Kept so that descriptors stay layout-compatible. */
     void* workspace;
@@ -277,10 +289,6 @@ int mlpk_token_gemm_ln_post(int dtype, const void* x, int ldx, int M, int S, con
                             int ldr, int res_mode, const float* post_scale, const float* post_shift, void* out, int ldo, int t_rows, void* stream);
 int mlpk_stats_finalize_planar(const float* part, int64_t rows, int nplanes, int64_t plane_stride, int group, int64_t count, float eps,
                                float* mean, float* rstd, void* stream);
-/* Tuning hook (tools/tokenmlp_timeline.py), not part of the forward path: when `buf` is non-NULL, later mlpk_token_mlp
- * launches log per-workgroup s_memtime stamps into it (64 x uint64 per workgroup); NULL switches the logging off.
- * The only library-held state, and off by default. */
-void mlpk_token_mlp_debug(void* buf);
 
 /* ---- patch gather (im2col of a kernel==stride convolution) -----------------------------
  * out[(b*Hp + hp)*Wp + wp][k], row stride ldo (>= K, pad columns [K, ldo) are zero-filled).

@@ -12,8 +12,6 @@ Only the instructions the generator uses are implemented; an unknown mnemonic ra
 """
 import struct
 
-import os
-
 import numpy as np
 
 POISON = 0x7FC0DEAD
@@ -343,16 +341,13 @@ class Emu:
     # ---- asynchronous completion
     # Stores are modelled as the operations that complete FIRST (out of issue order): adversarial for any wait that would count them.
     # The family's documented behaviour is in-order completion for loads and stores alike (LLVM AMDGPUUsage, memory model GFX6-GFX9 /
-    # GFX90A / GFX942: "completion is reported to a wavefront in execution order"); STORES_IN_ORDER = True models that -- needed only by
-    # kernels generated with MLPK_Q4_COUNT_STORES=1 (a round-6 experiment that measured no gain).
-    STORES_IN_ORDER = os.environ.get("MLPK_Q4_COUNT_STORES", "0") == "1"
+    # GFX90A / GFX942: "completion is reported to a wavefront in execution order"); no generated kernel counts its stores, so the model
+    # keeps the adversarial order.
 
     def wait_vm(self, w, n):
-        """in issue order, as late as allowed (STORES_IN_ORDER = False: adversarial for counted stores -- stores complete first)"""
+        """in issue order, as late as allowed (stores complete first: adversarial for counted stores)"""
         while len(w.vm) > n:
-            k = None if self.STORES_IN_ORDER else next((i for i, (kind, _) in enumerate(w.vm) if kind == "store"), None)
-            if k is None:
-                k = 0
+            k = next((i for i, (kind, _) in enumerate(w.vm) if kind == "store"), 0)
             _, fn = w.vm.pop(k)
             if fn:
                 fn()

@@ -25,7 +25,7 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from isa import A, F, H, S, V, Abs, Asm, Neg, Reg, h2bits  # noqa: E402
+from isa import A, F, H, S, V, Asm, Neg, Reg, h2bits  # noqa: E402
 
 # the 16-bit GELU polynomials of mlpk_common.h (MLPK_GELUP_*) by storage type.  f16: (scale, Horner coefficients) of the centred form
 # t = clamp(x * scale, -sqrt2, sqrt2), u = t * t - 1; bf16: (clamp, coefficients) of the raw form t = clamp(x, -clamp, clamp), u = t * t
@@ -34,13 +34,12 @@ GELU = {"f16": (0.314269681, [0.00260713836, -0.00718860654, 0.00979797821, -0.0
         "bf16": (4.0, [-1.58078628e-09, 1.21711111e-07, -4.10086659e-06, 8.06673925e-05, -0.00104820437, 0.00966487452, -0.0661753789,
                        0.39884752])}
 GELU_RAW = {"f16": False, "bf16": True}
-# round 4, bf16 grade: gelu(x) = x / (1 + 2^(x (k0 + k1 |x| + k2 x^2)))  (mlpk_common.h MLPK_GELUS_K*, tools/fit_gelu_sig.py): SEVEN
-# instructions per element instead of eleven (two of them transcendental: ~2 extra cycles each beside an MFMA, tools/ubench/q4_slots.py).
-# MLPK_GELU_BF16_POLY=1 at generation time (+ -DMLPK_GELU_BF16_POLY for the HIP sources) keeps the polynomial for A/B builds.
+# round 4, bf16 grade: gelu(x) = x / (1 + 2^(x (k0 + k1 |x| + k2 x^2)))  (mlpk_common.h MLPK_GELUS_K*, tools/fit_gelu_sig.py).  The generated
+# kernels no longer emit it, nor the bf16 polynomial above: those constants stay as the record of the header's numbers.
 GELU_SIG = {"bf16": (-2.28684449, -0.0305621661, -0.0905431807)}
-# round 5: the default bf16 form is "h2b" -- Phi in packed f16 (GELU_H2 below), the product in fp32 on the unrounded x (mlpk_common.h gelu_h2b_f);
-# MLPK_GELU_BF16_SIG=1 / MLPK_GELU_BF16_POLY=1 at generation time (+ the -D of the same name for the HIP sources) keep the older forms for A/B builds
-GELU_FORM = {"f16": "poly", "bf16": "poly" if os.environ.get("MLPK_GELU_BF16_POLY") == "1" else ("sig" if os.environ.get("MLPK_GELU_BF16_SIG") == "1" else "h2b")}
+# round 5: the bf16 form is "h2b" -- Phi in packed f16 (GELU_H2 below), the product in fp32 on the unrounded x (mlpk_common.h gelu_h2b_f).
+# (The logistic and polynomial bf16 forms were generation-time A/B switches until ABI 14: profiles/r05_issue_slots_packed_gelu.txt.)
+GELU_FORM = {"f16": "poly", "bf16": "h2b"}
 
 
 # round 5, the fused token-mixing kernel's bf16 grade ("h2", t4gen.py): Phi as a polynomial in PACKED f16 -- two elements per instruction and no
@@ -98,29 +97,9 @@ def h2b_gelu_ops(E, x, hp, t, u, q, v_c, s_scale, s_c6, v_nz):
         E("v_fma_mix_f32", x[r], x[r], q[r >> 1], v_nz, op_sel="[0,%d,0]" % (r & 1), op_sel_hi="[0,1,0]")
 
 
-def sig_gelu_ops(E, x, q, v_k2, s_k1, s_k0):
-    """x[r] <- gelu(x[r]) for four chains abreast, the operation sequence of gelu16_f<bf16> (mlpk_common.h); q: one scratch register
-    per chain.  (A transcendental's result is read >= 4 instructions after it was written: the gfx940 forwarding hazard needs 1.)"""
-    for r in range(4):
-        E("v_fma_f32", q[r], Abs(x[r]), v_k2, s_k1)
-    for r in range(4):
-        E("v_fma_f32", q[r], Abs(x[r]), q[r], s_k0)
-    for r in range(4):
-        E("v_mul_f32", q[r], x[r], q[r])
-    for r in range(4):
-        E("v_exp_f32", q[r], q[r])
-    for r in range(4):
-        E("v_add_f32", q[r], F(1.0), q[r])
-    for r in range(4):
-        E("v_rcp_f32", q[r], q[r])
-    for r in range(4):
-        E("v_mul_f32", x[r], x[r], q[r])
 SQRT2 = 1.41421356237
 
 STAGE_B = 49152          # one LDS stage: A 256 x 128 B, then B 128 x 128 B
-# round 6: a workgroup's last block drains its last tile WITHOUT multiplying a dummy tile (Q4.build drain_only); MLPK_Q4_DRAIN_ONLY=0 at
-# generation time rebuilds the round-5 kernels (A/B)
-DRAIN_ONLY = os.environ.get("MLPK_Q4_DRAIN_ONLY", "1") != "0"
 B_OFF = 32768
 OUT_OFF = 3 * STAGE_B     # 4 x 4 KiB: one staging tile per wave for the stores
 LDS_BYTES = OUT_OFF + 16384
@@ -146,7 +125,7 @@ class Alloc:
 
 
 class Q4:
-    def __init__(self, dtype="bf16", gelu=False, ln=False, res=False, stats=False, nkf=4, dbg=0, name=None, static=False):
+    def __init__(self, dtype="bf16", gelu=False, ln=False, res=False, stats=False, nkf=4, name=None, static=False):
         assert nkf >= 2
         self.dtype, self.gelu, self.ln, self.res, self.stats, self.nkf = dtype, gelu, ln, res, stats, nkf
         # static (round 4): the kernel is built for ONE K = 64 * nkf with nkf % 3 == 0, so a tile always starts in LDS stage 0 and
@@ -155,11 +134,6 @@ class Q4:
         # FOUR LDS-DMA pieces -- the instruction's immediate offset moves both the global and the LDS address, tools/ubench/lds_dma_offset.hip)
         self.static = static
         assert not static or (nkf % 3 == 0 and nkf <= 32)
-        # tuning ablations (results are wrong by construction): 1 no LDS-DMA, 2 no stores, 4 no epilogue fillers, 8 no fragment reads,
-        # 16 minimal iteration tail (no stage rotation), 64 every tile stored over tile (0, 0); variants under test: A/B switches: 256 the four
-        # stores of a block row back to back (default: spread over the next block row), 512 ordinary instead of non-temporal stores
-        self.dbg = dbg
-        self.fillers_on, self.dma_on, self.stores_on, self.reads_on, self.tail_on = not (dbg & 4), not (dbg & 1), not (dbg & 2), not (dbg & 8), not (dbg & 16)
         self.name = name or "q4_%s%s%s%s_%s%d" % (dtype, "_gelu" if gelu else "", "_ln" if ln else "", "_res" if res else "", "s" if static else "f", nkf)
         self.a = Asm()
         self.mfma = "v_mfma_f32_32x32x16_bf16" if dtype == "bf16" else "v_mfma_f32_32x32x16_f16"
@@ -199,10 +173,9 @@ class Q4:
         if self.stats:
             self.s_part, self.s_partld = s("part", 2, 2), s("partld")
             self.s_eP = s("eP", 2, 2)
-        self.sig = self.gelu and GELU_FORM[self.dtype] == "sig"
         self.h2b = self.gelu and GELU_FORM[self.dtype] == "h2b"
-        self.s_r2 = s("r2") if (self.gelu and not self.sig and not self.h2b and not GELU_RAW[self.dtype]) else None      # sqrt 2: the centred polynomial's clamp
-        self.s_k0, self.s_k1 = (s("gk0"), s("gk1")) if (self.sig or self.h2b) else (None, None)      # (h2b: the packed scale and c6)
+        self.s_r2 = s("r2") if (self.gelu and not self.h2b) else None      # sqrt 2: the centred polynomial's clamp
+        self.s_k0, self.s_k1 = (s("gk0"), s("gk1")) if self.h2b else (None, None)      # (h2b: the packed scale and c6)
         # (prof1 = the end stamp, taken after the last block: it lives in the next-tile DMA base, which is dead by then)
         self.s_prof0, self.s_prof1, self.s_profp, self.s_ntiles = s("prof0", 2, 2), self.s_dAn, s("profp", 2, 2), s("ntiles")
         self.s_t = [s("t%d" % i) for i in range(6)]
@@ -365,8 +338,8 @@ class Q4:
                 for d_, n_ in ((self.s_dA, self.s_dAn), (self.s_dB, self.s_dBn)):
                     a("s_mov_b32", d_[0], n_[0])
                     a("s_mov_b32", d_[1], n_[1])
-            a("s_mov_b32", self.s_pm0, 0 if (self.dbg & 64) else self.s_cm0)       # (64: every tile is stored over tile (0, 0))
-            a("s_mov_b32", self.s_pn0, 0 if (self.dbg & 64) else self.s_cn0)
+            a("s_mov_b32", self.s_pm0, self.s_cm0)
+            a("s_mov_b32", self.s_pn0, self.s_cn0)
             a("s_mov_b32", self.s_cm0, self.s_nm0)
             a("s_mov_b32", self.s_cn0, self.s_nn0)
 
@@ -379,10 +352,7 @@ class Q4:
                 a("s_sub_u32", t[0], self.k["nk"], self.nkf)
                 a("s_cmp_lg_u32", self.s_left, 0)
                 a("s_cselect_b32", self.s_roll, t[0], 0)
-        ops = self.capture(shift) + self.epi_bases_ops()
-        if self.fillers_on:
-            ops += self.param_load_ops()
-        return ops + self.capture(nxt)
+        return self.capture(shift) + self.epi_bases_ops() + self.param_load_ops() + self.capture(nxt)
 
     def param_load_ops(self):
         """the column / row parameters (and the residual tile) of the drained tile, as loads"""
@@ -431,23 +401,15 @@ class Q4:
 
     def gelu_ops(self, E, x, t, u, q):
         """x[r] <- gelu(x[r]) for the 4 chains abreast (the operation sequence of gelu16_f in mlpk_common.h)"""
-        if self.sig:
-            return sig_gelu_ops(E, x, q, self.v_c0, self.s_k1, self.s_k0)
         if self.h2b:
             return h2b_gelu_ops(E, x, self._hp, t, u, q, [self.v_c0] + self.v_hc, self.s_k0, self.s_k1, self.v_nz)
-        scale, c = GELU[self.dtype]
-        if GELU_RAW[self.dtype]:
-            for r in range(4):
-                E("v_med3_f32", t[r], x[r], F(-scale), F(scale))
-            for r in range(4):
-                E("v_mul_f32", u[r], t[r], t[r])
-        else:
-            for r in range(4):
-                E("v_mul_f32", t[r], F(scale), x[r])
-            for r in range(4):
-                E("v_med3_f32", t[r], t[r], Neg(self.s_r2), self.s_r2)
-            for r in range(4):
-                E("v_fma_f32", u[r], t[r], t[r], F(-1.0))
+        scale, c = GELU[self.dtype]       # (f16: the centred polynomial)
+        for r in range(4):
+            E("v_mul_f32", t[r], F(scale), x[r])
+        for r in range(4):
+            E("v_med3_f32", t[r], t[r], Neg(self.s_r2), self.s_r2)
+        for r in range(4):
+            E("v_fma_f32", u[r], t[r], t[r], F(-1.0))
         for r in range(4):
             E("v_fmaak_f32", q[r], u[r], self.v_c0, F(c[1]))
         for k in range(2, len(c)):
@@ -527,11 +489,7 @@ class Q4:
                 ops.append(lambda k=k, i=i: (a("s_mov_b32", "exec_lo", 0x11111111), a("s_mov_b32", "exec_hi", 0x11111111),
                                              a("global_store_dwordx2", self.voffP[k], sp, self.s_eP, offset=i * 256),
                                              a("s_mov_b64", "exec", -1)) and None)
-            if self.stores_on:
-                if not (self.dbg & 512):
-                    E("global_store_dwordx4", self.voffC[k], o, self.s_eC, nt=True)
-                else:
-                    E("global_store_dwordx4", self.voffC[k], o, self.s_eC)
+            E("global_store_dwordx4", self.voffC[k], o, self.s_eC, nt=True)
             if k == 3:
                 ops.extend(self.capture(lambda: self.add64(self.s_eC, self.s_eC, self.s_rowC)))
                 if self.res and i + 2 < 4:
@@ -565,11 +523,8 @@ class Q4:
                     E(self.cvt, pk[0], x[0], x[1])
                     E(self.cvt, pk[1], x[2], x[3])
                     ops.append(lambda c=4 * j + g, pk=pk: self.ds("ds_write_b64", self.v_stw[c], pk))
-                    if i > 0 and not (self.dbg & 256):
-                        if (4 * j + g) in (1, 3, 5, 7):
-                            store_part(i - 1, (4 * j + g) >> 1)
-                    elif i > 0 and j == 0 and g == 1:
-                        stores(i - 1)
+                    if i > 0 and (4 * j + g) in (1, 3, 5, 7):
+                        store_part(i - 1, (4 * j + g) >> 1)
             rd = [None] * 4
             self._st_reads[i] = rd
             for k in range(4):
@@ -582,21 +537,20 @@ class Q4:
         """advance the DMA stream and the LDS stages (issued in the gaps of the last k-step: every piece of the iteration has been
         issued by then, the fragment reads of the step use the old addresses until its sixth MFMA)"""
         a, t = self.a, self.s_t
-        if not self.tail_on or self.static:
+        if self.static:
             return [], []
 
         def salu():
             E = a
-            if self.dma_on:
-                self.add64(self.s_dA, self.s_dA, 128)
-                self.add64(self.s_dB, self.s_dB, 128)
-                E("s_sub_u32", self.s_dcnt, self.s_dcnt, 1)
-                E("s_cmp_eq_u32", self.s_dcnt, 0)
-                E("s_cselect_b32", self.s_dA[0], self.s_dAn[0], self.s_dA[0])
-                E("s_cselect_b32", self.s_dA[1], self.s_dAn[1], self.s_dA[1])
-                E("s_cselect_b32", self.s_dB[0], self.s_dBn[0], self.s_dB[0])
-                E("s_cselect_b32", self.s_dB[1], self.s_dBn[1], self.s_dB[1])
-                E("s_cselect_b32", self.s_dcnt, self.k["nk"], self.s_dcnt)
+            self.add64(self.s_dA, self.s_dA, 128)
+            self.add64(self.s_dB, self.s_dB, 128)
+            E("s_sub_u32", self.s_dcnt, self.s_dcnt, 1)
+            E("s_cmp_eq_u32", self.s_dcnt, 0)
+            E("s_cselect_b32", self.s_dA[0], self.s_dAn[0], self.s_dA[0])
+            E("s_cselect_b32", self.s_dA[1], self.s_dAn[1], self.s_dA[1])
+            E("s_cselect_b32", self.s_dB[0], self.s_dBn[0], self.s_dB[0])
+            E("s_cselect_b32", self.s_dB[1], self.s_dBn[1], self.s_dB[1])
+            E("s_cselect_b32", self.s_dcnt, self.k["nk"], self.s_dcnt)
             # stages: rd <- rd + 1, wr <- wr + 1 (mod 3)   (t[5] is the tail's own scratch register)
             for r in (self.s_rd, self.s_wr):
                 E("s_add_u32", r, r, STAGE_B)
@@ -659,7 +613,7 @@ class Q4:
             new_ready = {}
             for qm in range(8):
                 i, j = qm >> 1, qm & 1
-                if j == 0 and s > 0 and self.reads_on and (not self.static or i in (0, 2)):
+                if j == 0 and s > 0 and (not self.static or i in (0, 2)):
                     # first use of A_i (and of both B fragments when i == 0: they were read before A_0); the fragments of step 0
                     # were waited for in front of the previous barrier.  Static kernels wait twice per step instead of four times
                     # (for A_1 in front of MFMA 0, for A_3 in front of MFMA 4: the reads were issued 5 / 3 MFMAs earlier) -- every
@@ -667,7 +621,7 @@ class Q4:
                     self.wait_lds(ready[("A", i if not self.static else i + 1)])
                 d = self.acc(acc_set, 2 * i + j)
                 slot = dma_slots.get((s, qm))
-                if slot and self.dma_on:
+                if slot:
                     kind, pc = slot
                     if not self.static:
                         a("s_add_u32", "m0", self.s_wrA if kind == "A" else self.s_wrB, pc * 1024)
@@ -675,7 +629,7 @@ class Q4:
                         self.dma_m0(kind, pc // 4, d_slab, d_stage)
                 csrc = 0 if (zero_c and s == 1) else d
                 a(self.mfma, d, self.FB[mbuf][j], self.FA[mbuf][i], csrc)
-                if slot and self.dma_on:
+                if slot:
                     kind, pc = slot
                     if self.static:
                         base = ((self.s_dAn if d_next else self.s_dA) if kind == "A" else (self.s_dBn if d_next else self.s_dB))
@@ -684,7 +638,7 @@ class Q4:
                         self.vload("global_load_lds_dwordx4", self.voffA[pc], self.s_dA)
                     else:
                         self.vload("global_load_lds_dwordx4", self.voffB[pc], self.s_dB)
-                if qm < 6 and self.reads_on:
+                if qm < 6:
                     kind, idx = read_order[qm]
                     if self.static:
                         # stages 0 / 1: immediate offsets of the first base; stage 2: the second base
@@ -715,22 +669,12 @@ class Q4:
                 rest.pop(0)()
         # vmcnt in front of the barrier: the pieces of the PREVIOUS iteration must have landed (<= 12 loads of this one may be
         # in flight: loads return in order, stores may not be counted on), and so must every VGPR load issued in this one
-        # Round 6 experiment, kept as an option (MLPK_Q4_COUNT_STORES=1 at generation time; the emulator then needs STORES_IN_ORDER): counting
-        # this iteration's STORES in the wait as well.  A wave's vector-memory operations report completion in issue order on this family
-        # (LLVM AMDGPUUsage, memory model GFX6-GFX9 / GFX90A / GFX942), so vmcnt(operations issued in this iteration) would be enough
-        # for "everything older has completed"; counting the loads only also covers this iteration's first pieces, one per store behind
-        # them.  Hypothesis: that is what makes gMLP's proj1 (K = 256: 16 stores per 4 slabs) run 144 us in the model against 83 alone.
-        # Measured same-box, three alternations (profiles/r06_q4_count_stores_ab.txt): gMLP-S 9.932 / 9.946 / 9.928 against 9.939 / 9.940 /
-        # 9.912 ms, Mixer-B/16 7.39 vs 7.40, ViP-S7 27.81 vs 27.62 (-0.6 %), ResMLP-24 5.07 vs 5.07: nothing -- the slab waits are not
-        # what the stores hold up.  Default off.
-        count_stores = os.environ.get("MLPK_Q4_COUNT_STORES", "0") == "1"
-        kinds = [("load" if x.op.startswith("global_load_dword") else ("store" if x.op.startswith("global_store") else "dma"))
-                 for x in a.ins[i_start:] if x.op.startswith("global_load") or (count_stores and x.op.startswith("global_store"))]
+        # (Counting this iteration's stores in the wait as well was measured neutral and removed in ABI 14: profiles/r06_q4_count_stores_ab.txt.)
+        kinds = [("load" if x.op.startswith("global_load_dword") else "dma") for x in a.ins[i_start:] if x.op.startswith("global_load")]
         allow = len(kinds)
         if "load" in kinds:
             allow = len(kinds) - 1 - max(k for k, x in enumerate(kinds) if x == "load")
-        cap = 63 if count_stores else 12
-        a("s_waitcnt", vmcnt=min(allow, cap if self.dma_on else 0), lgkmcnt=0)
+        a("s_waitcnt", vmcnt=min(allow, 12), lgkmcnt=0)
         a("s_barrier")
 
     # ------------------------------------------------------------------ the kernel
@@ -767,12 +711,7 @@ class Q4:
         a("v_xor_b32", x, x, h)                    # ^ k-half of the lane
         if self.s_r2 is not None:
             a("s_mov_b32", self.s_r2, F(SQRT2))
-        if self.sig:
-            gk = GELU_SIG[self.dtype]
-            a("v_mov_b32", self.v_c0, F(gk[2]))
-            a("s_mov_b32", self.s_k1, F(gk[1]))
-            a("s_mov_b32", self.s_k0, F(gk[0]))
-        elif self.h2b:
+        if self.h2b:
             a("v_mov_b32", self.v_c0, h2bits(GELU_H2["coefs"][0]))
             for cj in range(5):
                 a("v_mov_b32", self.v_hc[cj], h2bits(GELU_H2["coefs"][cj + 1]))
@@ -941,9 +880,8 @@ class Q4:
             a("s_cmp_eq_u32", self.s_left, 0)
             a("s_cbranch_scc1", L_end)
             a("s_sub_u32", self.s_left, self.s_left, 1)
-            if DRAIN_ONLY:
-                a("s_cmp_eq_u32", self.s_left, 0)
-                a("s_cbranch_scc1", L_drain[1])
+            a("s_cmp_eq_u32", self.s_left, 0)
+            a("s_cbranch_scc1", L_drain[1])
             a("s_branch", L_block[1])
         else:
             a("s_mov_b32", self.s_wr, 0)
@@ -979,7 +917,7 @@ class Q4:
             """tile multiplied into set P, set 1 - P drained"""
             a.label(L_block[P])
             # --- unrolled iterations with the fillers
-            ops = (self.epilogue_ops(1 - P) if self.fillers_on else [])
+            ops = self.epilogue_ops(1 - P)
             head = self.block_start_ops()
             ngaps = (self.nkf - 1) * 32
             state = {"done": 0, "gap": 0}
@@ -1014,10 +952,9 @@ class Q4:
             a("s_cmp_eq_u32", self.s_left, 0)
             a("s_cbranch_scc1", L_end)
             a("s_sub_u32", self.s_left, self.s_left, 1)
-            if DRAIN_ONLY:
-                # no tile left to multiply: the draining block WITHOUT its dummy tile (round 6)
-                a("s_cmp_eq_u32", self.s_left, 0)
-                a("s_cbranch_scc1", L_drain[1 - P])
+            # no tile left to multiply: the draining block WITHOUT its dummy tile (round 6)
+            a("s_cmp_eq_u32", self.s_left, 0)
+            a("s_cbranch_scc1", L_drain[1 - P])
             # fall through / jump to the other parity
 
         def drain_only(Q):
@@ -1029,7 +966,7 @@ class Q4:
             drain itself, straight through -- no operand stream, no barrier (the staging tile is the wave's own)."""
             a.label(L_drain[Q])
             head = self.block_start_ops()
-            ops = self.epilogue_ops(1 - Q) if self.fillers_on else []
+            ops = self.epilogue_ops(1 - Q)
             for qm in range(8):
                 i, j = qm >> 1, qm & 1
                 d = self.acc(1 - Q, 2 * i + j)
@@ -1050,12 +987,12 @@ class Q4:
         a("s_branch", L_block[1])          # (block 1 follows in the listing; kept explicit)
         block(1)
         a("s_branch", L_block[0])
-        if DRAIN_ONLY:
-            drain_only(0)
-            drain_only(1)
+        drain_only(0)
+        drain_only(1)
         a.label(L_end)
         a("s_waitcnt", vmcnt=0, lgkmcnt=0)
-        # tuning: prof != 0 -> wave 0 of every workgroup stores (cycles of the whole kernel body, tiles)
+        # prof != 0 -> wave 0 of every workgroup stores (cycles of the whole kernel body, tiles).  The host passes null since ABI 14 (the cycle
+        # counts were a tuning aid); the code stays so that the kernels' instructions do not change
         L_np = a.newlabel("NOPROF")
         a("s_memtime", self.s_prof1)
         a("s_cmp_eq_u32", self.s_profp[0], 0)
@@ -1095,11 +1032,6 @@ def variants():
                 yield "q4_%s_%s_f%d" % (dt, cls, nkf), dict(dtype=dt, gelu=gelu, ln=ln, res=res, stats=stats, nkf=nkf)
             for nk in NK_STATIC:
                 yield "q4_%s_%s_s%d" % (dt, cls, nk), dict(dtype=dt, gelu=gelu, ln=ln, res=res, stats=stats, nkf=nk, static=True)
-    # tuning ablations (wrong results by construction; bits in Q4.__init__)
-    for cls, nkf in (("gl", 12), ("r", 12)):
-        gelu, ln, res, _ = CLASSES[cls]
-        for x in (1, 2, 3, 4, 5, 13, 21, 29, 64, 65, 256, 512, 768):
-            yield "q4_bf16_%s_f%d_x%d" % (cls, nkf, x), dict(dtype="bf16", gelu=gelu, ln=ln, res=res, nkf=nkf, dbg=x)
 
 
 def kernel_text(name, gen):
@@ -1122,12 +1054,11 @@ def emit(path):
             raise RuntimeError("%s: %d hazard lint findings, first: %s" % (name, len(pr), pr[0]))
         out.append(kernel_text(name, g))
         table.append((name, kw))
-    out.append("namespace mlpk {\nstruct Q4Variant { const char* name; const void* fn; int dtype, gelu, ln, res, stats, nkf, dbg, is_static; };\n"
+    out.append("namespace mlpk {\nstruct Q4Variant { const char* name; const void* fn; int dtype, gelu, ln, res, stats, nkf, is_static; };\n"
                "static const Q4Variant kQ4Variants[] = {\n")
     for name, kw in table:
-        dbg = kw.get("dbg", 0)
-        out.append("    {\"%s\", reinterpret_cast<const void*>(&%s), %s, %d, %d, %d, %d, %d, %d, %d},\n" %
-                   (name, name, "MLPK_BF16" if kw["dtype"] == "bf16" else "MLPK_F16", kw["gelu"], kw["ln"], kw["res"], kw.get("stats", False), kw["nkf"], dbg,
+        out.append("    {\"%s\", reinterpret_cast<const void*>(&%s), %s, %d, %d, %d, %d, %d, %d},\n" %
+                   (name, name, "MLPK_BF16" if kw["dtype"] == "bf16" else "MLPK_F16", kw["gelu"], kw["ln"], kw["res"], kw.get("stats", False), kw["nkf"],
                     kw.get("static", False)))
     out.append("};\n}  // namespace mlpk\n")
     text = "".join(out)

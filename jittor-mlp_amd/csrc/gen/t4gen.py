@@ -29,7 +29,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa import A, F, S, V, Asm, Neg, Reg, h2bits  # noqa: E402
-from q4gen import GELU, GELU_FORM, GELU_H2, GELU_RAW, GELU_SIG, SQRT2, Alloc, h2_gelu_ops, h2b_gelu_ops, sig_gelu_ops  # noqa: E402
+from q4gen import GELU, GELU_FORM, GELU_H2, SQRT2, Alloc, h2_gelu_ops, h2b_gelu_ops  # noqa: E402
 
 KA = dict(xt=0, w1=8, w2=16, b1=24, b2=32, x=40, stats=48, prof=56,
           M=64, G=68, ldxt=72, ldx=76, ntiles=80, tpi=84, tpi_magic=88, grid=92, stat_ld=96, nit=100, lead=104, S=108,
@@ -59,7 +59,7 @@ class T4:
     NXA = 8                                # X fragments kept in the 32 AGPRs the accumulators leave over
     DEPTH = 3                              # W fragments read ahead of their MFMAs (ring of 4 register quads)
 
-    def __init__(self, dtype="bf16", stats=False, dbg=0, name=None, shape=0, ln=False, h2=False):
+    def __init__(self, dtype="bf16", stats=False, name=None, shape=0, ln=False, h2=False):
         # ln: the token LayerNorm + transpose is this kernel's X loader -- x itself is read (token-major rows, statistics given),
         # normalised, transposed through LDS into the fragment registers; `xt` is not used (shaped kernels only)
         assert not ln or shape
@@ -68,9 +68,7 @@ class T4:
         # (>= 2): the fill and drain iterations are emitted without the stages that have nothing to do, the next tile's X is
         # requested two iterations before the tile ends
         self.shape = shape
-        # tuning ablations (wrong results by construction): 1 no LDS-DMA, 2 no GELU fillers, 4 no epilogue stores, 16 no residual loads,
-        # 32 no X loads
-        self.dtype, self.stats, self.dbg = dtype, stats, dbg
+        self.dtype, self.stats = dtype, stats
         # h2 (round 5, bf16 storage only; mlpk.h layout 3): the GELU in packed f16 and the hidden KEPT in f16 -- W2 is packed as f16 and the second
         # product runs on the f16 MFMA; x, W1, the first product and everything the kernel stores stay bf16
         assert not h2 or dtype == "bf16"
@@ -80,7 +78,6 @@ class T4:
         self.mfma2 = "v_mfma_f32_32x32x16_f16" if h2 else self.mfma          # the second product
         self.cvt = "v_cvt_pk_bf16_f32" if dtype == "bf16" else "v_cvt_pk_f16_f32"
         self.dot = "v_dot2c_f32_bf16" if dtype == "bf16" else "v_dot2c_f32_f16"
-        self.raw = GELU_RAW[dtype]
         self.coefs = GELU[dtype][1]
         self.a = Asm()
         self.build()
@@ -101,9 +98,8 @@ class T4:
         self.s_scur = s("scur", 2, 2) if self.stats else None
         self.s_tok8 = s("tok8")
         self.s_r2 = s("r2")
-        self.sig = GELU_FORM[self.dtype] == "sig" and not self.h2
         self.h2b = GELU_FORM[self.dtype] == "h2b" and not self.h2         # (layout 2 of a bf16 model: the library-wide bf16 GELU, the hidden bf16)
-        self.s_k0, self.s_k1 = (s("gk0"), s("gk1")) if (self.sig or self.h2b) else (None, None)
+        self.s_k0, self.s_k1 = (s("gk0"), s("gk1")) if self.h2b else (None, None)
         # packed-f16 constants: two in SGPRs (as many as the logistic form held -- the asm block may clobber no more scalar registers than
         # that: "inline assembly requires more registers than available"), c0 .. c5 in VGPRs
         self.s_hscale, self.s_hc6 = (s("hscale"), s("hc6")) if self.h2 else (None, None)
@@ -198,7 +194,8 @@ class T4:
         """xg[par_in] (fc1 + b1 of a group, the accumulator layout) -> h[par_out][rb][kk] (A fragments of the second product).
         Plain fp32 VALU operations, four independent chains abreast: v_pk_*_f32 would halve the count but does not overlap with
         the matrix pipe (one v_pk_fma_f32 between two MFMAs costs 17 cycles, tools/ubench/q4_slots.py, profiles/r03_t4_issue_slots.txt).
-        The operation sequence of gelu16_f (mlpk_common.h): bf16 11 operations per element (raw form), f16 15 (centred form)."""
+        The operation sequence of gelu16_f (mlpk_common.h) for f16 (centred form, 15 operations per element); bf16 takes gelu_h2b_f, or the
+        packed-f16 form of layout 3."""
         a = self.a
         ops = []
 
@@ -215,23 +212,15 @@ class T4:
                     # accumulator registers (4 grp + 2 k, 4 grp + 2 k + 1) -> the packed pair (e0 >> 1) + k of A fragment kk
                     h2_gelu_ops(E, x, [hreg[(e0 >> 1) + k] for k in range(2)], T[0:2], U[0:2], Q[0:2], self.v_c0, self.s_hscale, self.v_hc + [self.s_hc6])
                     continue
-                if self.sig:
-                    sig_gelu_ops(E, x, Q, self.v_c0, self.s_k1, self.s_k0)
-                elif self.h2b:
+                if self.h2b:
                     h2b_gelu_ops(E, x, self.v_hp, T[0:2], U[0:2], Q[0:2], [self.v_c0] + self.v_hc, self.s_k0, self.s_k1, self.v_nz)
-                elif self.raw:
-                    for r in range(4):
-                        E("v_med3_f32", T[r], x[r], F(-scale), F(scale))
-                    for r in range(4):
-                        E("v_mul_f32", U[r], T[r], T[r])
-                else:
+                else:                                  # (f16: the centred polynomial)
                     for r in range(4):
                         E("v_mul_f32", T[r], F(scale), x[r])
                     for r in range(4):
                         E("v_med3_f32", T[r], T[r], Neg(self.s_r2), self.s_r2)
                     for r in range(4):
                         E("v_fma_f32", U[r], T[r], T[r], F(-1.0))
-                if not self.sig and not self.h2b:
                     for r in range(4):
                         E("v_fmaak_f32", Q[r], U[r], self.v_c0, F(c[1]))
                     for kx in range(2, len(c)):
@@ -304,11 +293,9 @@ class T4:
         a("s_waitcnt", vmcnt=vm_allow, lgkmcnt=0)
         a("s_barrier")
         self.lgkm_issued = 0
-        fill = [] if ((self.dbg & 2) or not gelu) else self.gelu_ops(1 - par, 1 - par)
-        dma = [] if (self.dbg & 1) else [(kind, i) for i in range(5) for kind in ("w1", "w2")]
-        xl = []
-        if xload and not (self.dbg & 32):
-            xl = [(rb, ks) for rb in range(2) for ks in range(self.NKS)]
+        fill = self.gelu_ops(1 - par, 1 - par) if gelu else []
+        dma = [(kind, i) for i in range(5) for kind in ("w1", "w2")]
+        xl = [(rb, ks) for rb in range(2) for ks in range(self.NKS)] if xload else []
         state = {"done": 0, "gap": 0}
         frs = ([("w2", kk, tb) for kk in range(2) for tb in range(self.NTB)] if fc2 else []) + \
               ([("w1", ks, None) for ks in range(self.NKS)] if fc1 else [])
@@ -395,8 +382,6 @@ class T4:
         self.add64(self.s_xb[1], self.s_xb[0], t[0])
 
     def x_loads(self):
-        if self.dbg & 32:
-            return
         for rb in range(2):
             for ks in range(self.NKS):
                 self.vload("global_load_dwordx4", self.X[rb][ks], self.v_xoff, self.s_xb[rb], offset=32 * ks)
@@ -552,9 +537,6 @@ class T4:
         if rounds == 1:
             a("s_mov_b64", "exec", self.s_mask)               # tokens 192..195: lanes 0..31 of round 0
         for r in range(rounds):
-            if self.dbg & 16:
-                rec.append(self.vm_loads - 1)
-                continue
             rec.append(self.vload("global_load_dwordx4", self.e_res[tb & 1][r], self.v_ooff, self.s_lcur))
             self.add64(self.s_lcur, self.s_lcur, self.s_tok8)
         if rounds == 1:
@@ -619,12 +601,11 @@ class T4:
                     a("global_store_dwordx2", self.v_soff, sp, self.s_scur)
                     a("s_mov_b64", "exec", -1)
                     self.add64(self.s_scur, self.s_scur, 64)
-                if not (self.dbg & 4):
-                    if rounds == 1:
-                        a("s_mov_b64", "exec", self.s_mask)
-                    a("global_store_dwordx4", self.v_ooff, rr, self.s_ocur)
-                    if rounds == 1:
-                        a("s_mov_b64", "exec", -1)
+                if rounds == 1:
+                    a("s_mov_b64", "exec", self.s_mask)
+                a("global_store_dwordx4", self.v_ooff, rr, self.s_ocur)
+                if rounds == 1:
+                    a("s_mov_b64", "exec", -1)
                 self.add64(self.s_ocur, self.s_ocur, self.s_tok8)
             if tb + 2 < self.NTB:
                 res[tb + 2] = self.res_loads(tb + 2)
@@ -668,10 +649,6 @@ class T4:
             a("s_mov_b32", self.s_k0, h2bits(GELU_H2["scale"]))
             a("s_mov_b32", self.s_k1, h2bits(GELU_H2["coefs"][6]))
             a("v_mov_b32", self.v_nz, 0x80000000)
-        elif self.sig:
-            a("v_mov_b32", self.v_c0, F(GELU_SIG[self.dtype][2]))
-            a("s_mov_b32", self.s_k1, F(GELU_SIG[self.dtype][1]))
-            a("s_mov_b32", self.s_k0, F(GELU_SIG[self.dtype][0]))
         else:
             a("v_mov_b32", self.v_c0, F(self.coefs[0]))
         a("s_mov_b32", self.s_mask[0], -1)
@@ -742,12 +719,11 @@ class T4:
         # ---- the first stages and the first tile's X
         a("s_sub_u32", t[0], 0, k["lead"])
         self.dma_sources()
-        if not (self.dbg & 1):
-            for i in range(5):
-                for kind in ("w1", "w2"):
-                    self.emit_m0(kind, i, 0)
-                    a("s_nop", 0)
-                    self.emit_dma(kind, i, 0)
+        for i in range(5):
+            for kind in ("w1", "w2"):
+                self.emit_m0(kind, i, 0)
+                a("s_nop", 0)
+                self.emit_dma(kind, i, 0)
         if self.ln:
             self.ln_loader(self.s_tile)
         else:
@@ -756,7 +732,7 @@ class T4:
         a("s_sub_u32", t[0], 2, k["lead"])
         a("s_lshl_b32", t[0], t[0], 7)
         a("v_add_u32", self.v_b1rd, t[0], self.v_b1rd)              # bias row of the first iteration's group
-        a("s_waitcnt", vmcnt=0 if ((self.dbg & 33) or self.ln) else 10 + 2 * self.NKS)   # b2 (the loads before the 10 DMA pieces and the X quads)
+        a("s_waitcnt", vmcnt=0 if self.ln else 10 + 2 * self.NKS)   # b2 (the loads before the 10 DMA pieces and the X quads)
         a.label(L_tile)
         self.tile_scalars()
         for rb in range(2):
@@ -773,7 +749,7 @@ class T4:
                         for r in range(4):
                             a("v_mov_b32", self.h[par][rb][kk][r], 0)
         a("s_sub_u32", self.s_g, 0, k["lead"])
-        nx = 0 if ((self.dbg & 32) or self.ln) else 2 * self.NKS
+        nx = 0 if self.ln else 2 * self.NKS
         xl_on = not self.ln
         if self.shape == 0:
             a("s_lshr_b32", self.s_cnt, k["nit"], 1)
@@ -863,7 +839,8 @@ class T4:
         else:
             a("s_cbranch_scc1", L_tile)
         a.label(L_end)
-        # tuning: shader cycles of this workgroup -> prof[bid] (mlpk_token_mlp_debug), skipped when the pointer is null
+        # shader cycles of this workgroup -> prof[bid], skipped when the pointer is null.  The host passes null since ABI 14 (the cycle counts
+        # were a tuning aid, mlpk_token_mlp_debug); the code stays so that the kernels' instructions do not change
         L_noprof = a.newlabel("NOPROF")
         a("s_memtime", self.s_t64)
         a("s_or_b32", t[0], p["prof"][0], p["prof"][1])
@@ -901,8 +878,6 @@ def variants():
             out.append(dict(dtype="bf16", stats=st, shape=shape, h2=True))
         for shape in (1, 2):
             out.append(dict(dtype="bf16", stats=st, shape=shape, ln=True, h2=True))
-    for dbg in (1, 2, 4, 3, 16, 32, 48, 52):
-        out.append(dict(dtype="bf16", stats=True, dbg=dbg, name="t4_bf16_st_dbg%d" % dbg))
     return out
 
 
@@ -926,11 +901,11 @@ def emit(path):
             raise RuntimeError("%s: %d hazard lint findings, first: %s" % (g.name, len(pr), pr[0]))
         out.append(kernel_text(g))
         table.append((g.name, kw))
-    out.append("namespace mlpk {\nstruct T4Variant { const char* name; const void* fn; int dtype, stats, dbg, shape, ln, h2; };\n"
+    out.append("namespace mlpk {\nstruct T4Variant { const char* name; const void* fn; int dtype, stats, shape, ln, h2; };\n"
                "static const T4Variant kT4Variants[] = {\n")
     for name, kw in table:
-        out.append("    {\"%s\", reinterpret_cast<const void*>(&%s), %s, %d, %d, %d, %d, %d},\n" %
-                   (name, name, "MLPK_BF16" if kw["dtype"] == "bf16" else "MLPK_F16", kw["stats"], kw.get("dbg", 0), kw.get("shape", 0), kw.get("ln", False),
+        out.append("    {\"%s\", reinterpret_cast<const void*>(&%s), %s, %d, %d, %d, %d},\n" %
+                   (name, name, "MLPK_BF16" if kw["dtype"] == "bf16" else "MLPK_F16", kw["stats"], kw.get("shape", 0), kw.get("ln", False),
                     kw.get("h2", False)))
     out.append("};\n}  // namespace mlpk\n")
     text = "".join(out)

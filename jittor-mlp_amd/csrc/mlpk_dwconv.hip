@@ -769,9 +769,8 @@ extern "C" int mlpk_dwconv_nhwc(int dtype, const void* x, void* out, int B, int 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int es = dtype == MLPK_F32 ? 4 : 2;
     const bool fast_ok = (C % (16 / es) == 0) && (((uintptr_t)x & 15) == 0) && B <= 0x7fffffff;
-    // matrix-pipe form: 16-bit dtypes, maps of up to 32 x 32, whole 8-channel groups (MLPK_DWCONV_NO_MFMA: tuning hook for A/B runs)
-    static const bool no_mfma = getenv("MLPK_DWCONV_NO_MFMA") != nullptr;
-    if (fast_ok && !no_mfma && es == 2 && H <= 32 && W <= 32 && C % 8 == 0 && (((uintptr_t)out & 15) == 0)) {
+    // matrix-pipe form: 16-bit dtypes, maps of up to 32 x 32, whole 8-channel groups
+    if (fast_ok && es == 2 && H <= 32 && W <= 32 && C % 8 == 0 && (((uintptr_t)out & 15) == 0)) {
         const int rc = dtype == MLPK_F16 ? dwconv_mfma_launch<f16_t>(k, x, out, B, H, W, C, w, bias, bn_scale, bn_shift, s)
                                          : dwconv_mfma_launch<bf16_t>(k, x, out, B, H, W, C, w, bias, bn_scale, bn_shift, s);
         if (rc != DW_NOFIT) return rc;

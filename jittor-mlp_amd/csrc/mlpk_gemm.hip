@@ -45,11 +45,8 @@ struct GemmArgs {
     int vec_c, vec_r;   // vector (4-element) store / residual-load allowed
     // p8 launch (see gemm_nt_p8_kernel): row panels [m_base, m_base + panels * tile height), column groups
     int m_base, panels, cgroups;
-    int rev;            // p8: walk the row panels from the last to the first (tuning: MLPK_P8_REVERSE)
     void* prof_buf;     // MLPK_P8_PROF builds: per-workgroup cycle sums (reserved & 8)
-    int dbg_delay;      // de-phase sleep, units of 8128 cycles
-    int dbg_q4;         // tuning bits of the generated q4 kernels (desc.reserved bits 16..23)
-    int dbg;            // tuning ablations (desc.reserved): 1 = no main loop, 2 = no stores, 4 = no epilogue
+    int dbg;            // tuning bits (desc.reserved & 0xff, mlpk.h)
     // by-product row statistics of the stored values (16-bit row-major outputs): pair (q, m) = (sum, sum of squares) of row m over
     // column block q; block width 128 (LDS-staged epilogue) or 32 (direct epilogue of the persistent tile).  PLANAR, one plane per
     // column block: a tile's pairs are one contiguous run (256 rows x 8 bytes), written as whole cache lines -- interleaved per
@@ -79,8 +76,6 @@ __device__ __forceinline__ void glds_piece(const void* gsrc, unsigned lds_dst) {
                  : "v"(gsrc), "s"(lds_dst)
                  : "memory");
 }
-
-__device__ unsigned g_cu_ticket[2048];
 
 template <typename T> struct Mma;
 // `pinned` = the same instruction as volatile inline asm: it keeps its place between the barriers / waits /
@@ -801,22 +796,6 @@ __device__ __forceinline__ void gemm_nt_s3_body(const GemmArgs& p, const int bid
     const int a_rd = (wm * TM + frow) * 64 + co;
     const int b_rd = BM * 64 + (wn * TN + frow) * 64 + co;
 
-    // ---- de-phase the two workgroups that share a CU (tuning flag dbg & 16) ----
-    // Both start together and would run main loop / epilogue in lockstep, leaving the matrix pipe idle
-    // during both epilogues.  The second arriver on a CU (per-CU ticket, first launch round only) sleeps
-    // for about one epilogue, so that from then on one workgroup's VALU/store phase overlaps the other's MFMAs.
-    if ((p.dbg & 16) && bid < 512) {
-        if (tid == 0) {
-            const unsigned hw = __builtin_amdgcn_s_getreg((15 << 11) | (0 << 6) | 4);     // HW_REG_HW_ID[15:0]
-            const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);    // HW_REG_XCC_ID[3:0]
-            const unsigned key = ((xcc & 7) << 8) | ((hw >> 8) & 0xff);                   // cu / sh / se bits
-            const unsigned ticket = atomicAdd(&g_cu_ticket[key], 1u);
-            if (ticket & 1) {
-                for (int i = 0; i < p.dbg_delay; ++i) __builtin_amdgcn_s_sleep(127);
-            }
-        }
-        __syncthreads();
-    }
     MLPK_STAMP(0);
     if (nk > 0) S3_STAGE(0);
     if (nk > 1) S3_STAGE(1);
@@ -1430,7 +1409,7 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
     auto setup = [&](const int li) {
         const int u = u0 + li;
         const int panel = __builtin_amdgcn_readfirstlane(u / cg_s);
-        m0 = p.m_base + (p.rev ? p.panels - 1 - panel : panel) * BM;
+        m0 = p.m_base + panel * BM;
         n0 = (ncol0 + (u - panel * cg_s)) * BN;
         tileA = reinterpret_cast<const char*>(p.A) + uniform64((size_t)m0 * p.lda * 2u);
         tileB = reinterpret_cast<const char*>(p.B) + uniform64((size_t)n0 * p.ldb * 2u);
@@ -1748,25 +1727,14 @@ static int p8_grid_cap() {
 // rounds; cost model per round: w_h = (365 + 512 NI) / 2413 of a 256-row round (fixed per-slab cost of the barriers and the
 // B operand + MFMA time), plus a fixed cost per extra launch.  Exhaustive search over (r4, r3, r2, r1).
 struct P8Plan { int n; int ni[4]; int panels[4]; };
-static const double* p8_weights() {
-    // time of one round of NI * 64-row tiles relative to a 256-row round; MLPK_P8_W="w1,w2,w3" overrides (calibration runs)
-    static double w[5] = {0.0, 0.37, 0.58, 0.79, 1.0};
-    static bool init = false;
-    if (!init) {
-        init = true;
-        if (const char* e = getenv("MLPK_P8_W")) {
-            double a, b, c;
-            if (sscanf(e, "%lf,%lf,%lf", &a, &b, &c) == 3) { w[1] = a; w[2] = b; w[3] = c; }
-        }
-    }
-    return w;
-}
+// time of one round of NI * 64-row tiles relative to a 256-row round
+static const double kP8Weight[5] = {0.0, 0.37, 0.58, 0.79, 1.0};
 
 // 0 = mixed tile heights (the shortest single launch), 1 = whole 256-row tiles only (the least total CU time): mlpk_gemm_set_plan
 static int g_p8_plan_mode = 0;
 
 static P8Plan p8_plan(int M, int tiles_n, int nk, int G, bool mixed, double* cost_out = nullptr) {
-    const double* w = p8_weights();
+    const double* w = kP8Weight;
     // whole tiles where that still fills a round of CUs (a launch with fewer tiles than CUs keeps its mixed heights: gMLP's N = 256 product) and the
     // tiles are long (K >= 1024: a short tile is mostly fixed cost, and more, lower tiles then pack better -- ResMLP's K = 384 fc1 loses 7 %)
     if (g_p8_plan_mode == 1 && (long long)(M / 256) * tiles_n >= G && nk >= 16) mixed = false;
@@ -1781,11 +1749,6 @@ static P8Plan p8_plan(int M, int tiles_n, int nk, int G, bool mixed, double* cos
     double best_cost = rounds(m / 4) + (m % 4 ? w[m % 4] * rounds(1) : 0.0) + (best.n - 1) * launch_pen;
     if (cost_out) *cost_out = best_cost;
     if (!mixed) return best;
-    static const int force_ni = getenv("MLPK_P8_FORCE_NI") ? atoi(getenv("MLPK_P8_FORCE_NI")) : 0;     // calibration runs: one height
-    if (force_ni >= 1 && force_ni <= 4 && m % force_ni == 0) {
-        best.n = 1; best.ni[0] = force_ni; best.panels[0] = m / force_ni;
-        return best;
-    }
     const int rmax = rounds(m / 4) + 1;
     auto cap = [&](int r) { return (int)((long long)r * G / tiles_n); };      // panels that fit r rounds
     for (int r4 = 0; r4 <= rmax; ++r4)
@@ -1828,6 +1791,12 @@ static int p8_cgroups(int tiles_n, int K, int es) {
     return 1;
 }
 
+// test hook, read per call: MLPK_P8_PAIR=0 launches the panels of a plan one height at a time (tests/test_gpu_ops.py holds both bit-equal)
+static bool p8_pair_on() {
+    const char* e = getenv("MLPK_P8_PAIR");
+    return !(e && e[0] == '0');
+}
+
 // what the persistent tile accepts (everything else goes to the other pipelines): 16-bit row-major output in whole tiles
 static bool p8_eligible(const GemmArgs& a, int es, bool trans) {
     if (es != 2 || trans || a.rscale || a.vec_c != 2 || (a.res_mode != MLPK_RES_NONE && a.vec_r != 2)) return false;
@@ -1861,8 +1830,7 @@ template <typename T> static int launch_p8(const GemmArgs& a0, bool trans, hipSt
             const int Q = (U + X - 1) / X;
             return 8 * (Q < cap / 8 ? Q : cap / 8);
         };
-        const char* pe = getenv("MLPK_P8_PAIR");
-        const bool pair_on = !(pe && pe[0] == '0');                                                   // A/B aid
+        const bool pair_on = p8_pair_on();
         for (int s = 0; s < plan.n; ++s) {
             const int ni = plan.ni[s];
             a.m_base = m_base;
@@ -1945,8 +1913,6 @@ static bool q4_call_of(const GemmArgs& a, int dtype, bool trans, Q4Call& c) {
     c.gelu = a.act == MLPK_ACT_GELU; c.ln = a.ln_mean != nullptr; c.res = a.res_mode != MLPK_RES_NONE;
     c.row_part = a.row_part; c.row_part_ld = a.row_part_ld;
     c.one_group = (a.dbg & 128) != 0;
-    c.dbg = (a.dbg & (31 | 64)) | (a.dbg_q4 << 8);
-    c.prof = (a.dbg & 32) ? a.prof_buf : nullptr;      // reserved & 32: cycle counts into desc.workspace
     return q4_supported(c);
 }
 
@@ -2088,15 +2054,7 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
     a.act = d->act; a.res_mode = d->res_mode;
     a.t_rows = d->t_rows; a.t_tokens = d->t_tokens;
     a.dbg = d->reserved & 0xff;
-    a.dbg_delay = (d->reserved >> 8) & 0xff;
-    a.dbg_q4 = (d->reserved >> 16) & 0xff;
     a.m_base = 0; a.panels = 0; a.cgroups = 1; a.prof_buf = d->workspace;
-    {
-        // tuning (round 4): the persistent tile walks its row panels backwards when its A operand is larger than the Infinity Cache and was
-        // just written front to back by the previous kernel (channel-MLP fc2 reading the 308 MB hidden): the rows written last are read first
-        static const int rev_mode = getenv("MLPK_P8_REVERSE") ? atoi(getenv("MLPK_P8_REVERSE")) : 0;
-        a.rev = rev_mode == 2 || (rev_mode == 1 && (long long)d->M * d->K * es > (200ll << 20)) ? 1 : 0;
-    }
     a.row_part = d->row_part; a.row_part_ld = d->row_part_ld;
     const int vb = 4 * es;   // bytes of a 4-element vector
     a.vec_c = (d->ldc % 4 == 0) && (((uintptr_t)d->C % vb) == 0);
@@ -2113,14 +2071,12 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
     algo = d->algo;
     const bool glds_ok = d->K % (4 * epc) == 0;      // K a multiple of half a 128-byte slab
     // the persistent tile is auto-selected where its overlapped epilogue applies (16-bit row-major, no row scale)
-    static const bool no_p8 = getenv("MLPK_GEMM_NO_P8") != nullptr;      // tuning hook: A/B the tile choice in one run
-    bool p8_ok = !no_p8 && p8_eligible(a, es, trans);
+    bool p8_ok = p8_eligible(a, es, trans);
     // ... and with statistics, where the direct epilogue instantiates them: bias + residual (the GEMMs that produce a residual stream)
     const bool p8_stats_ok = d->res_mode != MLPK_RES_NONE && d->act == MLPK_ACT_NONE && !d->ln_mean && !d->cscale && !d->cshift && !(a.dbg & 64);
     if (stats && !p8_stats_ok) p8_ok = false;
     if (algo == 0) {
-        // round 3: the generated one-wave-per-SIMD tile where it is ahead (MLPK_GEMM_Q4=0 switches it off for A/B runs; 2 = wherever
-        // it applies).  Rule from the per-shape A/B of every GEMM call of the bs=256 models (profiles/r03_gemm_shapes_q4_ab_v1.txt,
+        // round 3: the generated one-wave-per-SIMD tile where it is ahead.  Rule from the per-shape A/B of every GEMM call of the bs=256 models (profiles/r03_gemm_shapes_q4_ab_v1.txt,
         // r03_q4_probe_v3.txt):
         //  * where the persistent 256 x 256 tile cannot run (N % 256 != 0: the N = 384 / 1152 / 640 / 128 shapes of ViP, S2-MLP, Swin-,
         //    Hire-, CycleMLP, ResMLP) it replaces the s3 tile: 0.69-0.94 of its time on every measured shape;
@@ -2128,17 +2084,15 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
         //    at N = 768 with short K (0.80-0.87: three column tiles fill the persistent tile's rounds badly), behind elsewhere (short K
         //    with many column tiles 1.05-1.10; K >= 3072 1.10: its LDS-DMA runs two 48-KiB slabs ahead, HBM-latency bound on long K);
         //  * its pipeline spends one extra (draining) block per workgroup: only grids of several tiles per CU.
-        static const int q4_mode = getenv("MLPK_GEMM_Q4") ? atoi(getenv("MLPK_GEMM_Q4")) : 1;
         Q4Call qc;
-        // (... and only when a generated kernel exists for the call's class AND its tuning bits: reserved bits meant for the persistent
-        //  tile, or a forced MLPK_Q4_NKF, must fall through to the other tiles instead of failing the call)
-        if (q4_mode && q4_call_of(a, d->dtype, trans, qc) && q4_variant_name(qc)) {
+        // (... and only when a generated kernel exists for the call's class: the others fall through to the other tiles)
+        if (q4_call_of(a, d->dtype, trans, qc) && q4_variant_name(qc)) {
             const long long tiles = (long long)(d->M / 256) * (d->N / 128);
             bool take = false;
             if (!p8_ok) take = tiles >= 512;
             else take = (d->act == MLPK_ACT_GELU && d->K >= 640 && d->K <= 1280 && d->N >= 3072 && tiles >= 2048) ||
                         (d->N == 768 && d->K <= 512 && tiles >= 1024);
-            if (q4_mode >= 2 || take) algo = 15;
+            if (take) algo = 15;
         }
     }
     if (algo == 0) algo = auto_algo(d->M, d->N, d->K, epc, glds_ok, p8_ok, stats);
@@ -2171,8 +2125,7 @@ extern "C" int mlpk_gemm_kernel_name(const mlpk_gemm_desc* d, char* buf, int len
         // the persistent tile: which template runs follows from the plan of tile heights (launch_p8)
         const bool staged = (a.dbg & 64) != 0 || (a.res_mode != MLPK_RES_NONE && (a.act == MLPK_ACT_GELU || a.ln_mean));
         const P8Plan plan = p8_plan(a.M, a.N / 256, a.K / 64, p8_grid_cap(), !staged && !(a.dbg & 16));
-        const char* pe = getenv("MLPK_P8_PAIR");
-        const bool pair_on = !(pe && pe[0] == '0');
+        const bool pair_on = p8_pair_on();
         const bool pair = pair_on && !staged && plan.n >= 2 && ((plan.ni[0] == 4 && plan.ni[1] < 4) || (plan.ni[1] == 4 && plan.ni[0] < 4));
         char hs[32] = "";
         for (int s = 0, o = 0; s < plan.n && o < 28; ++s) o += snprintf(hs + o, sizeof(hs) - (size_t)o, "%s%d", s ? "+" : "", plan.ni[s] * 64);
@@ -2274,9 +2227,8 @@ extern "C" int mlpk_gemm_nt_pair(const mlpk_gemm_desc* d0, const mlpk_gemm_desc*
     if (rc) return rc;
     rc = gemm_prepare(d1, a1, algo1, t1);
     if (rc) return rc;
-    static const bool off = getenv("MLPK_GEMM_PAIR") && atoi(getenv("MLPK_GEMM_PAIR")) == 0;      // A/B aid: two launches
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (!off && algo0 == algo1 && algo0 >= 11 && algo0 <= 13 && !t0 && !t1 && d0->dtype == d1->dtype && d0->dtype != MLPK_F32 &&
+    if (algo0 == algo1 && algo0 >= 11 && algo0 <= 13 && !t0 && !t1 && d0->dtype == d1->dtype && d0->dtype != MLPK_F32 &&
         !(a0.dbg | a1.dbg)) {
 #define MLPK_PAIR(TT)                                                                  \
     switch (algo0) {                                                                   \

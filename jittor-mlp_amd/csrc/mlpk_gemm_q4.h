@@ -21,13 +21,11 @@ struct Q4Call {
     int gelu, ln, res;
     float* row_part;           // by-product (sum, sum of squares) of the stored rows per block of 64 columns (mlpk.h row_part), or null
     int row_part_ld;
-    int one_group;             // tuning: a single column group
-    void* prof;                // tuning: (cycles, tiles) of every workgroup, 8 bytes each, or null
-    int dbg;                   // tuning ablations: 1 = no LDS-DMA, 4 = no epilogue fillers (results are wrong by construction)
+    int one_group;             // a single column group (mlpk.h: reserved & 128)
 };
 
 bool q4_supported(const Q4Call& c);
-// name of the generated kernel q4_launch would run for this call (nullptr: no variant for this class / its tuning bits)
+// name of the generated kernel q4_launch would run for this call (nullptr: no variant for this class)
 const char* q4_variant_name(const Q4Call& c);
 int q4_launch(const Q4Call& c, hipStream_t stream);
 

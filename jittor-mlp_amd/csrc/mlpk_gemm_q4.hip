@@ -21,7 +21,7 @@ struct Q4Args {
     int lda, ldb, ldc, ldr;
     int nk, cg, cg_magic, U;
     int Q, log2X, m_base, grid;
-    void* prof;          // tuning: per-workgroup (cycles, tiles) pairs, or null
+    void* prof;          // per-workgroup (cycles, tiles) pairs, or null: always null since ABI 14 (the kernels still test it)
     float* row_part;     // by-product row statistics (classes with stats): planes of 64 columns
     int row_part_ld;
     int pad[3];
@@ -71,30 +71,21 @@ bool q4_supported(const Q4Call& c) {
 }
 
 // the kernel for a call: the one built for exactly this K where there is one (round 4, Q4.static in q4gen.py: stage rotation, DMA
-// addressing and the tile switch resolved at generation time; MLPK_Q4_STATIC=0 switches them off for A/B runs), otherwise the
-// general kernel with the most unrolled (filler-carrying) iterations that K allows
-static const Q4Variant* q4_pick(const Q4Call& c, int force_nkf) {
-    static const bool use_static = !(getenv("MLPK_Q4_STATIC") && atoi(getenv("MLPK_Q4_STATIC")) == 0);
+// addressing and the tile switch resolved at generation time), otherwise the general kernel with the most unrolled (filler-carrying)
+// iterations that K allows
+static const Q4Variant* q4_variant(const Q4Call& c) {
     const int nk = c.K / 64;
     const Q4Variant* best = nullptr;
     for (const Q4Variant& v : kQ4Variants) {
-        if (v.dtype != c.dtype || v.gelu != c.gelu || v.ln != c.ln || v.res != c.res || v.stats != (c.row_part != nullptr) || v.dbg != c.dbg) continue;
+        if (v.dtype != c.dtype || v.gelu != c.gelu || v.ln != c.ln || v.res != c.res || v.stats != (c.row_part != nullptr)) continue;
         if (v.is_static) {
-            if (use_static && !force_nkf && v.nkf == nk) return &v;
+            if (v.nkf == nk) return &v;
             continue;
         }
         if (v.nkf > nk) continue;
-        if (force_nkf && v.nkf != force_nkf) continue;
         if (!best || v.nkf > best->nkf) best = &v;
     }
     return best;
-}
-
-static const Q4Variant* q4_variant(const Q4Call& c) {
-    const int force_nkf = getenv("MLPK_Q4_NKF") ? atoi(getenv("MLPK_Q4_NKF")) : 0;       // tuning: unrolled (filler) iterations
-    const Q4Variant* v = q4_pick(c, force_nkf);
-    if (!v && force_nkf) v = q4_pick(c, 0);
-    return v;
 }
 
 const char* q4_variant_name(const Q4Call& c) {
@@ -126,7 +117,7 @@ int q4_launch(const Q4Call& c, hipStream_t stream) {
     int lg = 0;
     while ((1 << lg) < X) ++lg;
     a.log2X = lg; a.m_base = 0; a.grid = grid;
-    a.prof = c.prof;
+    a.prof = nullptr;
     a.row_part = c.row_part; a.row_part_ld = c.row_part_ld;
     a.pad[0] = a.pad[1] = a.pad[2] = 0;
     hipError_t e = hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, Q4_LDS_BYTES);

@@ -910,7 +910,6 @@ static int mixshift_tile_launch(const MixShiftArgs& a, hipStream_t s, float* row
     int pitch = (strips - 1) * 8 + ((8 + kmax - 1 + 7) / 8) * 8;
     if (pitch < a.W + 2 * P) pitch = a.W + 2 * P;
     pitch = (pitch + 7) / 8 * 8;
-    static const int r_env = getenv("MLPK_MIXSHIFT_R") ? atoi(getenv("MLPK_MIXSHIFT_R")) : 0;       // tuning hook
     // rows per band: a thread holds at most MT_TMAX tasks of its >= 8 slots; among the heights whose tile leaves room for two workgroups
     // per CU, the one that stages the fewest rows (bands x (R + halo)) -- measured: 14 rows against 7 on the 28 x 28 and 14 x 14 maps
     // 188 -> 155 and 104 -> 79 us, 8 rows on the 56 x 56 map (one workgroup per CU) 362 -> 530
@@ -922,16 +921,12 @@ static int mixshift_tile_launch(const MixShiftArgs& a, hipStream_t s, float* row
         return ((size_t)MT_CB * pl + (size_t)R_ * a.W * MT_CB) * sizeof(T);
     };
     int R = 1, plane = 0;
-    if (r_env >= 1) {
-        R = r_env < r_cap ? r_env : r_cap;
-    } else {
-        long best = -1;
-        for (int r = r_cap; r >= 1; --r) {
-            int pl;
-            if (geometry(r, &pl) > 79 * 1024 && r > 1) continue;
-            const long cost = (long)((a.H + r - 1) / r) * (r + 2 * P);
-            if (best < 0 || cost < best) { best = cost; R = r; }
-        }
+    long best = -1;
+    for (int r = r_cap; r >= 1; --r) {
+        int pl;
+        if (geometry(r, &pl) > 79 * 1024 && r > 1) continue;
+        const long cost = (long)((a.H + r - 1) / r) * (r + 2 * P);
+        if (best < 0 || cost < best) { best = cost; R = r; }
     }
     const size_t lds = geometry(R, &plane);
     if (lds > 150 * 1024) return MT_NOT_TAKEN;
@@ -1376,7 +1371,7 @@ extern "C" int mlpk_swin_spatial_stats(int dtype, void* x, int B, int H, int W, 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     hipError_t e = hipSuccess;
     const int items = (t2 * (C / 8) + SW_NT - 1) / SW_NT, hpw = (heads + 3) / 4;
-    const char* q_env = getenv("MLPK_SWIN_SPATIAL_Q");                 // "0": the round-4 kernel (A/B runs, the bit-equality test)
+    const char* q_env = getenv("MLPK_SWIN_SPATIAL_Q");                 // test hook, read per call: "0" = the round-4 kernel (the bit-equality test)
     if (!(q_env && q_env[0] == '0')) {
         const int qitems = (((t2 + 3) / 4) * (C / 8) + SW_NT - 1) / SW_NT;
 #define SWQ_LAUNCH(TT, MAXQ, NHW)                                                                                          \
@@ -1481,9 +1476,8 @@ extern "C" int mlpk_mixshift_nhwc(int dtype, const void* x, void* out, int B, in
         if (rc0) return rc0;
     }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    static const bool no_band = getenv("MLPK_MIXSHIFT_NO_BAND") != nullptr;      // tuning hook
-    const char* tile_env = getenv("MLPK_MIXSHIFT_TILE");                         // "0": the per-chunk band kernel (A/B runs, the bit-equality test)
-    if (!no_band && !(tile_env && tile_env[0] == '0') && dtype != MLPK_F32) {
+    const char* tile_env = getenv("MLPK_MIXSHIFT_TILE");       // test hook, read per call: "0" = the per-chunk band kernel (the bit-equality test)
+    if (!(tile_env && tile_env[0] == '0') && dtype != MLPK_F32) {
         const int rc = dtype == MLPK_F16 ? mlpk::mixshift_tile_launch<mlpk::f16_t>(a, s) : mlpk::mixshift_tile_launch<mlpk::bf16_t>(a, s);
         if (rc != mlpk::MT_NOT_TAKEN) {
             if (rc) return rc;
@@ -1491,7 +1485,7 @@ extern "C" int mlpk_mixshift_nhwc(int dtype, const void* x, void* out, int B, in
             return 0;
         }
     }
-    if (!no_band && B <= 0x7fffff) {
+    if (B <= 0x7fffff) {
         int rc;
         switch (dtype) {
             case MLPK_F32: rc = mlpk::mixshift_band_launch<float>(a, s); break;

@@ -1052,7 +1052,7 @@ extern "C" int mlpk_convert(int src_dtype, int dst_dtype, const void* src, void*
     }
 }
 
-extern "C" int mlpk_abi_version(void) { return 13; }
+extern "C" int mlpk_abi_version(void) { return 14; }
 
 extern "C" const char* mlpk_strerror(int code) {
     switch (code) {

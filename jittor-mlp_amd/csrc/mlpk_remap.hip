@@ -823,11 +823,10 @@ extern "C" int mlpk_norm_shift_nhwc(int dtype, const void* in, void* out_w, void
     if (((uintptr_t)in | (uintptr_t)out_w | (uintptr_t)out_h) & 15) return MLPK_EALIGN;
     if (in == out_w || in == out_h) return MLPK_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // maps that fit the LDS: one workgroup per image, the activation evaluated once per element (MLPK_NORM_SHIFT_IMG=0: the gather form, A/B aid)
+    // maps that fit the LDS: one workgroup per image, the activation evaluated once per element (larger maps: the gather form below)
     const size_t img_bytes = (size_t)H * W * C * 2;
-    static const bool img_off = getenv("MLPK_NORM_SHIFT_IMG") && atoi(getenv("MLPK_NORM_SHIFT_IMG")) == 0;
     const size_t img_lds = img_bytes + (size_t)C * 8;                // + the per-channel scale / shift tables
-    if (!img_off && img_lds <= 160 * 1024 && (size_t)H * W * (C / 8) < (1u << 17)) {
+    if (img_lds <= 160 * 1024 && (size_t)H * W * (C / 8) < (1u << 17)) {
         hipError_t e = hipSuccess;
 #define NSI_LAUNCH(TT, GG)                                                                                                              \
     {                                                                                                                                   \
@@ -979,19 +978,15 @@ extern "C" int mlpk_vip_split_apply(int dtype, const void* zh, const void* zw, c
     const int64_t total = (int64_t)B * H * W * C;
     // 8 x 8 pixel tiles when the map is made of whole tiles, the runs are 16-byte aligned and the two staged tiles fit in LDS
     // channel split (round 6): as many workgroups per pixel tile as it takes for three of them to fit a CU's LDS (each takes whole groups,
-    // a multiple of 8 channels); MLPK_VIP_APPLY_PARTS overrides (A/B aid)
+    // a multiple of 8 channels)
     const int G = C / seg;
-    static const int parts_env = getenv("MLPK_VIP_APPLY_PARTS") ? atoi(getenv("MLPK_VIP_APPLY_PARTS")) : 0;
     int parts = 1;
     auto lds_of = [&](int pp) { return (size_t)2 * 8 * (G / pp) * 8 * seg * 2 + (size_t)3 * (C / pp) * 4; };
-    auto parts_ok = [&](int pp) { return pp >= 1 && G % pp == 0 && ((G / pp) * seg) % 8 == 0; };
-    if (parts_env > 0 && parts_ok(parts_env)) parts = parts_env;
-    else
-        for (int pp = 1; pp <= 4; ++pp)
-            if (parts_ok(pp)) { parts = pp; if (lds_of(pp) <= 52 * 1024) break; }
+    auto parts_ok = [&](int pp) { return G % pp == 0 && ((G / pp) * seg) % 8 == 0; };
+    for (int pp = 1; pp <= 4; ++pp)
+        if (parts_ok(pp)) { parts = pp; if (lds_of(pp) <= 52 * 1024) break; }
     const size_t lds_tile = lds_of(parts);
-    static const bool no_tile = getenv("MLPK_VIP_APPLY_NO_TILE") != nullptr;       // A/B aid
-    if (!no_tile && H % 8 == 0 && W % 8 == 0 && ldh % 8 == 0 && ldw % 8 == 0 && lds_tile <= 150 * 1024 && (int64_t)B * (H / 8) * (W / 8) * parts < 0x7fffffff &&
+    if (H % 8 == 0 && W % 8 == 0 && ldh % 8 == 0 && ldw % 8 == 0 && lds_tile <= 150 * 1024 && (int64_t)B * (H / 8) * (W / 8) * parts < 0x7fffffff &&
         (((uintptr_t)zh | (uintptr_t)zw) & 15) == 0) {
         const unsigned grid = (unsigned)((int64_t)B * (H / 8) * (W / 8) * parts);
         hipError_t e = hipSuccess;

@@ -28,7 +28,6 @@
 // LDS: 48 (W1 ring) + 48 (W2 ring) + 16 (H, double-buffered) + 32 (acc1 exchange / epilogue staging) + 4 (b1) + 0.9 (b2) = 149 KiB.
 #include "mlpk_common.h"
 #include "mlpk_tokenmlp_t4.h"
-#include <cstdlib>
 
 namespace mlpk {
 
@@ -42,7 +41,6 @@ struct TokenMlpArgs {
     int M, S, ks1, G;
     int ldxt, ldw2, ldx, t_rows;
     float* stats;       // optional: per (128-channel tile, token row) partial (sum, sum of squares) of the values written to x, planar
-    unsigned long long* dbg;   // tuning aid: per-workgroup [loop, epilogue] shader-clock sums (NULL in normal use)
 };
 
 // one 1-KiB LDS-DMA piece: uniform base + 32-bit per-lane offset, LDS destination = M0 base + lane * 16
@@ -190,8 +188,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
     if (tid < 16 * (TM_NB0 + TM_NB1)) b2s[tid] = tid < p.S ? p.b2[tid] : 0.f;
     __syncthreads();
 
-    unsigned long long t_loop = 0, t_epi = 0, ts = 0;
-    const bool stamp = p.dbg != nullptr;
     // Epilogue geometry.  A pass moves 32 token slots (0-15: the matrix wave's block j, 16-31: the activation wave's
     // block 8 + j) x 128 channels of fp32 (acc2 + b2) through LDS; reader thread = (slot tid >> 4, 8 channels tid & 15)
     // adds the residual in fp32, rounds ONCE and writes 16 bytes, i.e. whole 256-byte token rows per 16 lanes.
@@ -339,7 +335,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
             st = st == 2 ? 0 : st + 1;
         };
         for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-            if (stamp) ts = __builtin_readcyclecounter();
             // The X operands must have LANDED before the iteration loop, and the compiler must know it (a builtin, not
             // asm): otherwise its own "s_waitcnt vmcnt(n)" for them sits in front of their first use in EVERY
             // iteration, where it also drains the LDS-DMA pieces issued one iteration earlier.
@@ -354,7 +349,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
             for (; t < G; ++t) iter(ModeC<TM_STEADY>{}, t, tile);
             if (t == G) { iter(ModeC<TM_DRAIN>{}, t, tile); ++t; }       // (G == 1: the ramp already ran iteration G)
             iter(ModeC<TM_LAST>{}, t, tile);
-            if (stamp) { const unsigned long long n = __builtin_readcyclecounter(); t_loop += n - ts; ts = n; }
             // ---- tile epilogue ----
             // The residual tile (requested one iteration ago) must have landed HERE, with a wait the compiler knows about:
             // left to itself it waits vmcnt(0) in front of every pass's first use -- loads and stores share the counter and
@@ -377,7 +371,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
                 epilogue_reader(j, sb, res[j], rimg, rcc, row_ok);
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (stamp) { const unsigned long long n = __builtin_readcyclecounter(); t_epi += n - ts; ts = n; }
         }
     } else {
         // =============================== activation wave ===============================
@@ -489,11 +482,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
-    if (stamp && tid == 0) {
-        p.dbg[(size_t)blockIdx.x * 4 + 0] = t_loop;
-        p.dbg[(size_t)blockIdx.x * 4 + 1] = t_epi;
-        p.dbg[(size_t)blockIdx.x * 4 + 2] = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    }
 }
 
 // ====================================================================================================================
@@ -615,8 +603,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_rr_kernel(const TokenMlpArgs
     if (tid < 16 * T2_NB) b2s[tid] = tid < p.S ? p.b2[tid] : 0.f;
     __syncthreads();
 
-    unsigned long long t_loop = 0, t_epi = 0, ts = 0;
-    const bool stamp = p.dbg != nullptr;
     char* const stg = smem + T2_STG;
     const size_t srows = (size_t)(p.M / p.t_rows) * p.S;      // plane stride of the statistics pairs
 
@@ -704,7 +690,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_rr_kernel(const TokenMlpArgs
         constexpr bool LAG = decltype(lag_c)::value;
         load_x(blockIdx.x, lane_now());                    // (inside each half's own code: one live range per path)
         for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-            if (stamp) ts = __builtin_readcyclecounter();
             __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0): the X operands have landed, and the compiler knows it
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -746,7 +731,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_rr_kernel(const TokenMlpArgs
                 gelu(G - 1, ln);
                 fc2((s4 + 3) & 3, ln);
             }
-            if (stamp) { const unsigned long long n = __builtin_readcyclecounter(); t_loop += n - ts; ts = n; }
             // ---- tile epilogue ----
             // (per-lane epilogue geometry from a fresh lane id as well: nothing lane-derived lives across the iterations)
             const int le = lane_now();
@@ -806,16 +790,10 @@ __global__ void __launch_bounds__(512, 1) token_mlp_rr_kernel(const TokenMlpArgs
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (stamp) { const unsigned long long n = __builtin_readcyclecounter(); t_epi += n - ts; ts = n; }
         }
     };
     if (!lag) run(BoolC<false>{}); else run(BoolC<true>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // no LDS-DMA may outlive the workgroup
-    if (stamp && tid == 0) {
-        p.dbg[(size_t)blockIdx.x * 4 + 0] = t_loop;
-        p.dbg[(size_t)blockIdx.x * 4 + 1] = t_epi;
-        p.dbg[(size_t)blockIdx.x * 4 + 2] = (ntiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;
-    }
 }
 
 // ====================================================================================================================
@@ -1423,8 +1401,6 @@ __global__ void __launch_bounds__(512, 1) token_gemm_pipe_kernel(const TokenGemm
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-static unsigned long long* g_tm_dbg = nullptr;
-
 static int tm_grid_cap() {
     static int cap = 0;
     if (!cap) {
@@ -1439,27 +1415,18 @@ static int tm_grid_cap() {
 
 using namespace mlpk;
 
-extern "C" void mlpk_token_mlp_debug(void* buf) { g_tm_dbg = reinterpret_cast<unsigned long long*>(buf); }
-
 extern "C" int mlpk_token_mlp_chunk(void) { return 32; }
 
 // 1: W2 packed with the hidden columns of every group of 32 permuted (k slot 8 f + e <- column (e < 4 ? 4 f + e : 16 + 4 f + e - 4))
 // for the 256-row kernel that keeps the hidden in registers; 0: natural order (128-row kernel).
 extern "C" int mlpk_token_mlp_layout(int S, int nchunks) {
-    const char* e = getenv("MLPK_TOKEN_MLP_LAYOUT");
-    if (e && e[0] == '0') return 0;
     return (S <= 16 * T2_NB && nchunks * 32 <= TM_B1_FLOATS) ? 1 : 0;
 }
 
 // 2 when the generated one-wave-per-SIMD kernel (mlpk_tokenmlp_t4.hip) takes the shape, else mlpk_token_mlp_layout's answer.
 extern "C" int mlpk_token_mlp_layout_for(int dtype, int S, int nchunks, int t_rows) {
-    const char* e = getenv("MLPK_TOKEN_MLP_LAYOUT");
-    if (e && (e[0] == '0' || e[0] == '1')) return mlpk_token_mlp_layout(S, nchunks);
-    if (t4_supported(dtype, S, nchunks, ((S + 31) / 32) * 32, t_rows, t_rows, t_rows)) {
-        // 3 = layout 2 with the hidden kept in f16 (bf16 storage only; MLPK_T4_H2=0 keeps the all-bf16 kernels: A/B aid)
-        const char* h = getenv("MLPK_T4_H2");
-        return (dtype == MLPK_BF16 && !(h && h[0] == '0')) ? 3 : 2;
-    }
+    if (t4_supported(dtype, S, nchunks, ((S + 31) / 32) * 32, t_rows, t_rows, t_rows))
+        return dtype == MLPK_BF16 ? 3 : 2;      // 3 = layout 2 with the hidden kept in f16 (bf16 storage only)
     return mlpk_token_mlp_layout(S, nchunks);
 }
 
@@ -1478,10 +1445,8 @@ extern "C" int mlpk_token_mlp(int dtype, const void* xt, int ldxt, int M, int S,
         if (((uintptr_t)xt & 15) || ((uintptr_t)w1 & 15) || ((uintptr_t)w2 & 15) || ((uintptr_t)x & 15) || ((uintptr_t)b1 & 15)) return MLPK_EALIGN;
         T4Call c;
         c.dtype = dtype; c.M = M; c.S = S; c.G = nchunks; c.ldxt = ldxt; c.ldx = ldx; c.t_rows = t_rows;
-        c.xt = xt; c.w1 = w1; c.w2 = w2; c.b1 = b1; c.b2 = b2; c.x = x; c.stats = stats; c.prof = g_tm_dbg;
+        c.xt = xt; c.w1 = w1; c.w2 = w2; c.b1 = b1; c.b2 = b2; c.x = x; c.stats = stats;
         c.ln_mean = c.ln_rstd = c.gamma = c.beta = nullptr;
-        const char* d = getenv("MLPK_T4_DBG");
-        c.dbg = d ? atoi(d) : 0;
         c.h2 = layout == 3;
         return t4_launch(c, reinterpret_cast<hipStream_t>(stream));
     }
@@ -1497,7 +1462,6 @@ extern "C" int mlpk_token_mlp(int dtype, const void* xt, int ldxt, int M, int S,
     a.M = M; a.S = S; a.ks1 = ldxt / 32; a.G = nchunks;
     a.ldxt = ldxt; a.ldw2 = ldw2; a.ldx = ldx; a.t_rows = t_rows;
     a.stats = stats;
-    a.dbg = g_tm_dbg;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (layout == 1) {
         if (S > 16 * T2_NB) return MLPK_ESHAPE;
@@ -1554,9 +1518,8 @@ extern "C" int mlpk_token_mlp_ln(int dtype, void* x, int ldx, int M, int S, cons
         return MLPK_EALIGN;
     T4Call c;
     c.dtype = dtype; c.M = M; c.S = S; c.G = nchunks; c.ldxt = 224; c.ldx = ldx; c.t_rows = t_rows;
-    c.xt = nullptr; c.w1 = w1; c.w2 = w2; c.b1 = b1; c.b2 = b2; c.x = x; c.stats = stats; c.prof = g_tm_dbg;
+    c.xt = nullptr; c.w1 = w1; c.w2 = w2; c.b1 = b1; c.b2 = b2; c.x = x; c.stats = stats;
     c.ln_mean = ln_mean; c.ln_rstd = ln_rstd; c.gamma = gamma; c.beta = beta;
-    c.dbg = 0;
     c.h2 = layout == 3;
     return t4_launch(c, reinterpret_cast<hipStream_t>(stream));
 }
@@ -1574,9 +1537,8 @@ static int token_gemm_launch(int dtype, TokenGemmArgs& a, int res_mode, int lnl,
     }
 #define TG_RES(TT, LL)                                                                                                 \
     if (res_mode == MLPK_RES_ADD) TG_LAUNCH(TT, MLPK_RES_ADD, LL) else if (res_mode == MLPK_RES_MUL) TG_LAUNCH(TT, MLPK_RES_MUL, LL) else TG_LAUNCH(TT, MLPK_RES_NONE, LL)
-    // round 5: the operand-loader variants with >= 3 groups run as the two-iterations-deep pipeline (MLPK_TOKEN_GEMM_PIPE=0: the kernel above, A/B aid)
-    static const bool pipe_on = !(getenv("MLPK_TOKEN_GEMM_PIPE") && atoi(getenv("MLPK_TOKEN_GEMM_PIPE")) == 0);
-    const bool pipe_ok = lnl && pipe_on && a.G >= 3 && a.S % 2 == 0 && a.t_rows <= T5_TMAX && (!a.rscale || (a.rperiod % 8 == 0 && a.rperiod <= T5_TMAX)) &&
+    // round 5: the operand-loader variants with >= 3 groups run as the two-iterations-deep pipeline
+    const bool pipe_ok = lnl && a.G >= 3 && a.S % 2 == 0 && a.t_rows <= T5_TMAX && (!a.rscale || (a.rperiod % 8 == 0 && a.rperiod <= T5_TMAX)) &&
                          !(((uintptr_t)a.ln_mean | (uintptr_t)a.ln_rstd) & 7);
     if (a.post_scale && !(pipe_ok && a.t_rows <= T5_TMAX / 2)) return MLPK_ESHAPE;   // (the caller applies the Aff itself)
     if (pipe_ok) {      // (the statistics of a token pair are one 8-byte load)

@@ -20,8 +20,6 @@ struct T4Call {
     const float* ln_rstd;
     const float* gamma;        // (t_rows)
     const float* beta;
-    void* prof;                // tuning: shader cycles per workgroup (8 bytes each), or null
-    int dbg;                   // tuning ablations (wrong results by construction)
     int h2;                    // bf16 only (mlpk.h layout 3): GELU in packed f16, the hidden kept in f16, w2 holds f16 values
 };
 

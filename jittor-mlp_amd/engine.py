@@ -7,7 +7,6 @@ There is deliberately no CPU implementation: a non-GPU tensor raises NotImplemen
 the same error type the reference's Shift raises on CPU (shift_cuda.py:170-173).
 """
 import ctypes
-import os
 
 import threading
 
@@ -60,10 +59,10 @@ def set_side_streams(on):
 
 def side_stream(device):
     """One extra stream per device for small, latency-bound kernel chains that are independent of the big kernels issued next
-    (ViP's SplitAttention MLP beside the branch GEMMs); None when MLPK_NO_SIDE_STREAM=1.  Fork / join are events on both sides:
+    (ViP's SplitAttention MLP beside the branch GEMMs); None while set_side_streams(False).  Fork / join are events on both sides:
         ev = torch.cuda.Event(); ev.record(); with torch.cuda.stream(side): side.wait_event(ev); ...; done.record(side)
         ...; torch.cuda.current_stream().wait_event(done)"""
-    if not SIDE_STREAMS or os.environ.get("MLPK_NO_SIDE_STREAM", "0") == "1":
+    if not SIDE_STREAMS:
         return None
     key = (device.type, device.index)
     st = _SIDE.get(key)
@@ -75,7 +74,7 @@ def side_stream(device):
 class SideChain:
     """`with chain: <launches>` puts the launches on the device's side stream, ordered after everything issued so far on the
     current stream (fork event); `chain.join()` makes the current stream wait for them.  What runs inside must touch only buffers
-    that nothing issued between the `with` block and join() touches.  With MLPK_NO_SIDE_STREAM=1 the launches simply stay on
+    that nothing issued between the `with` block and join() touches.  With set_side_streams(False) the launches simply stay on
     the current stream."""
 
     def __init__(self, ws, name, device):
@@ -134,9 +133,7 @@ def pack_matrix(w, dtype, device, kpad=8):
 
 def embed_kpad(dtype):
     """K padding of a patch-embedding weight whose K is ragged (7 x 7 x 3 = 147): whole 64-byte slabs for the 16-bit dtypes, so that the product runs on the
-    LDS-DMA tiles instead of the register-staged fallback (ConvMixer-1536/20's embedding: 565 us at K = 152); MLPK_EMBED_KPAD overrides (A/B aid)"""
-    if os.environ.get("MLPK_EMBED_KPAD"):
-        return int(os.environ["MLPK_EMBED_KPAD"])
+    LDS-DMA tiles instead of the register-staged fallback (ConvMixer-1536/20's embedding: 565 us at K = 152)"""
     return 8 if dtype == torch.float32 else 32
 
 
@@ -204,7 +201,7 @@ def gemm(A, B, C, M, Nn, K, *, lda=None, ldb=None, ldc=None, bias=None, act=N.AC
     stats_finalize_planar, or None when the descriptor cannot deliver them (fp32, unaligned rows) and the caller runs row_stats."""
     if tag is not None and algo == 0:
         algo = GEMM_ALGO.get(tag, 0)
-    if GEMM_LOG is not None:                             # tuning: the distinct GEMM calls of a forward (tools/gemm_shapes.py)
+    if GEMM_LOG is not None:                             # tuning: the distinct GEMM calls of a forward
         GEMM_LOG.add((str(A.dtype), M, Nn, K, int(act), int(res), ln is not None, part is not None, cscale is not None or cshift is not None,
                       rscale is not None, int(out_mode), bias is not None))
     timed = TIMER is not None and tag is not None and not _defer
@@ -227,10 +224,10 @@ def gemm(A, B, C, M, Nn, K, *, lda=None, ldb=None, ldc=None, bias=None, act=N.AC
     d.t_rows, d.t_tokens, d.algo = t_rows, t_tokens, algo
     d.reserved = dbg
     d.workspace, d.workspace_bytes = None, 0             # unused since ABI 5 (no kernel needs scratch)
-    if prof is not None:                                 # tuning builds: per-workgroup cycle counters (reserved & 32 with algo 15)
+    if prof is not None:                                 # -DMLPK_P8_PROF builds: the persistent tile's per-workgroup cycle sums (reserved & 8)
         d.workspace, d.workspace_bytes = ptr(prof), prof.numel() * prof.element_size()
     out = None
-    if part is not None and epilogue_stats():
+    if part is not None:
         n = ctypes.c_int(0)
         if N.lib().mlpk_gemm_row_parts(ctypes.byref(d), ctypes.byref(n)) == 0:
             buf = part[0].get("%s.%d" % (part[1], n.value), (n.value, M, 2), torch.float32)     # (one buffer per plane count: no re-allocation)
@@ -262,9 +259,8 @@ def gemm_pair(first, second):
 
 
 def conv_gemm_nhwc_supported(dtype, Cin, kh, kw, stride, pad):
-    """mlpk_conv_gemm_nhwc: a strided convolution on channel-last rows as one product reading its operand through the window (MLPK_CONV_GEMM=0: window
-    gather + GEMM, A/B aid)"""
-    return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_CONV_GEMM", "1") != "0"
+    """mlpk_conv_gemm_nhwc: a strided convolution on channel-last rows as one product reading its operand through the window"""
+    return (dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_conv_gemm_nhwc_supported(dtype_code(dtype), Cin, kh, kw, stride, pad)))
 
 
@@ -304,26 +300,14 @@ def token_mlp_ln(x, ldx, M, S, mean, rstd, gamma, beta, w1, b1, w2, b2, nchunks,
                                       ptr(w2), w2.stride(0), ptr(b2), nchunks, t_rows, ptr(stats), layout, stream()), "mlpk_token_mlp_ln")
 
 
-def token_ln_fused():
-    """MLPK_TOKEN_LN_FUSED=0: LayerNorm + transpose as its own pass in front of the token kernel (A/B aid)."""
-    # (MLPK_T4_SHAPE=0 forces the generic token kernel, which has no LayerNorm loader: the unfused path then, not an error)
-    return os.environ.get("MLPK_TOKEN_LN_FUSED", "1") != "0" and os.environ.get("MLPK_T4_SHAPE", "") != "0"
-
-
 def layernorm_transpose_supported(dtype, C, ldx, ld_tt):
-    return dtype in (torch.float16, torch.bfloat16) and C % 128 == 0 and C <= 2048 and ldx % 8 == 0 and ld_tt % 8 == 0 \
-        and os.environ.get("MLPK_NO_FUSED_TOKEN_LN", "0") != "1"
+    return dtype in (torch.float16, torch.bfloat16) and C % 128 == 0 and C <= 2048 and ldx % 8 == 0 and ld_tt % 8 == 0
 
 
 def layernorm_transpose(x, nimg, S, C, gamma, beta, out_tt, ld_tt, eps=1e-5):
     """x: (nimg*S, >= C) with row stride x.stride(0) (a column slice of a wider tensor is fine)."""
     N.check(N.lib().mlpk_layernorm_transpose(dtype_code(x.dtype), ptr(x), nimg, S, C, x.stride(0), ptr(gamma), ptr(beta), eps,
                                              ptr(out_tt), ld_tt, stream()), "mlpk_layernorm_transpose")
-
-
-def epilogue_stats():
-    """MLPK_NO_EPILOGUE_STATS=1: separate statistics pass after the token kernel (A/B aid)."""
-    return os.environ.get("MLPK_NO_EPILOGUE_STATS", "0") != "1"
 
 
 def stats_finalize_planar(part, rows, count, mean, rstd, eps=1e-5, group=1):
@@ -356,17 +340,16 @@ def rows_to_nchw(cur, B, HW, C, out):
 
 
 def smlp_mix_supported(dtype, H, W, C):
-    """mlpk_smlp_mix (round 5): Sparse-MLP's BatchNorm + both axial mixes + the concatenation in one kernel (maps up to 32 x 32, 16 bit);
-    MLPK_SMLP_MIX=0 keeps the four-launch path (A/B aid)"""
-    if os.environ.get("MLPK_SMLP_MIX") == "0" or dtype not in (torch.float16, torch.bfloat16):
+    """mlpk_smlp_mix (round 5): Sparse-MLP's BatchNorm + both axial mixes + the concatenation in one kernel (maps up to 32 x 32, 16 bit)"""
+    if dtype not in (torch.float16, torch.bfloat16):
         return False
     return bool(N.lib().mlpk_smlp_mix_supported(dtype_code(dtype), H, W, C))
 
 
 def smlp_mix_dw_supported(dtype, H, W, C):
     """mlpk_smlp_mix_dw: the same with the block's depthwise 3 x 3 sublayer in front, for maps whose raw tile fits beside the transposed
-    copies (14 x 14, 7 x 7); MLPK_SMLP_MIX_DW=0: two kernels (A/B aid)"""
-    if os.environ.get("MLPK_SMLP_MIX_DW") == "0" or not smlp_mix_supported(dtype, H, W, C):
+    copies (14 x 14, 7 x 7)"""
+    if not smlp_mix_supported(dtype, H, W, C):
         return False
     return bool(N.lib().mlpk_smlp_mix_dw_supported(dtype_code(dtype), H, W, C))
 
@@ -394,7 +377,7 @@ def smlp_mix(x, ldx, B, H, W, C, bn_s, bn_h, wh, bh, ww, bw, out, ldo):
 
 
 def token_gemm_supported(dtype, S, sp):
-    return dtype in (torch.float16, torch.bfloat16) and S <= 224 and sp <= 224 and sp % 32 == 0 and os.environ.get("MLPK_NO_TOKEN_GEMM", "0") != "1"
+    return dtype in (torch.float16, torch.bfloat16) and S <= 224 and sp <= 224 and sp % 32 == 0
 
 
 def pack_token_gemm(w, b, dtype, device):
@@ -416,17 +399,14 @@ def token_gemm(xt, ldxt, M, S, wp, bp, ng, out, ldo, t_rows, *, R=None, ldr=0, r
 
 
 def token_gemm_ln_supported(dtype, S, t_rows, ldx):
-    """mlpk_token_gemm_ln: the LayerNorm / Aff in front of a token-mixing product as the kernel's operand loader
-    (MLPK_TOKEN_GEMM_LN=0: the separate normalise-and-transpose pass, A/B aid)"""
-    return (token_gemm_supported(dtype, S, round_up(S, 32)) and t_rows % 32 == 0 and ldx % 8 == 0
-            and os.environ.get("MLPK_TOKEN_GEMM_LN", "1") != "0")
+    """mlpk_token_gemm_ln: the LayerNorm / Aff in front of a token-mixing product as the kernel's operand loader"""
+    return token_gemm_supported(dtype, S, round_up(S, 32)) and t_rows % 32 == 0 and ldx % 8 == 0
 
 
 def token_gemm_ln_post_supported(dtype, S, t_rows, ldx):
     """mlpk_token_gemm_ln_post: the per-channel affine that FOLLOWS the sublayer applied where its result is stored -- the pipelined kernel only
-    (>= 3 groups of 32 tokens, an even token count, <= 1024 channels per image); MLPK_TOKEN_GEMM_POST=0: a separate mlpk_norm_apply (A/B aid)"""
-    return (token_gemm_ln_supported(dtype, S, t_rows, ldx) and S > 64 and S % 2 == 0 and t_rows <= 1024
-            and os.environ.get("MLPK_TOKEN_GEMM_POST", "1") != "0" and os.environ.get("MLPK_TOKEN_GEMM_PIPE", "1") != "0")
+    (>= 3 groups of 32 tokens, an even token count, <= 1024 channels per image)"""
+    return token_gemm_ln_supported(dtype, S, t_rows, ldx) and S > 64 and S % 2 == 0 and t_rows <= 1024
 
 
 def token_gemm_ln(x, ldx, M, S, mean, rstd, gamma, beta, wp, bp, ng, out, ldo, t_rows, *, R=None, ldr=0, res=N.RES_NONE, rscale=None, rperiod=0,
@@ -499,8 +479,8 @@ def pack_token_mlp(w1, b1, w2, b2, dtype, device, sp, layout=None, t_rows=None):
 
 
 def swin_spatial_supported(dtype, C, heads, ws):
-    """mlpk_swin_spatial: the spatial-MLP half of a Swin-MLP block in one kernel (MLPK_SWIN_SPATIAL_FUSED=0: the five passes, A/B aid)"""
-    return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_SWIN_SPATIAL_FUSED", "1") != "0"
+    """mlpk_swin_spatial: the spatial-MLP half of a Swin-MLP block in one kernel"""
+    return (dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_swin_spatial_supported(dtype_code(dtype), C, heads, ws)))
 
 
@@ -527,8 +507,8 @@ def swin_spatial(x, B, H, W, C, ws, pad_t, pad_l, Hp, Wp, heads, mean, rstd, gam
 
 
 def channel_mlp_fused_supported(dtype, C, hidden):
-    """mlpk_channel_mlp: the whole channel MLP of a narrow stage in one kernel (MLPK_CHANNEL_MLP_FUSED=0: the two GEMMs, A/B aid)"""
-    return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_CHANNEL_MLP_FUSED", "1") != "0"
+    """mlpk_channel_mlp: the whole channel MLP of a narrow stage in one kernel"""
+    return (dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_channel_mlp_supported(dtype_code(dtype), C, round_up(hidden, 32))))
 
 
@@ -573,7 +553,7 @@ def channel_mlp_fused(x, rows, C, pack, out, *, R=None, ln=None, ln_group=1, par
     does, for finalize_stats / stats_finalize_planar; None otherwise."""
     w1p, b1p, csum, w2p, b2p, nch = pack
     buf = None
-    if part is not None and epilogue_stats():
+    if part is not None:
         buf = part[0].get("%s.1" % part[1], (1, rows, 2), torch.float32)
     N.check(N.lib().mlpk_channel_mlp(dtype_code(x.dtype), ptr(x), x.stride(0), rows, C, ptr(ln[0]) if ln else None, ptr(ln[1]) if ln else None,
                                      ln_group, ptr(csum) if ln else None, ptr(w1p), w1p.stride(0), ptr(b1p), ptr(w2p), w2p.stride(0), ptr(b2p), nch,
@@ -587,8 +567,8 @@ def patchify(src, out, B, Cin, H, W, ph, pw, pad, ldo, layout=N.LAYOUT_NCHW, px_
 
 
 def patch_embed4_supported(src_dtype, dst_dtype, cin, H, W, C):
-    """mlpk_patch_embed4: Conv2d(3 -> C, k = stride = 4) (+ LayerNorm) in one kernel (MLPK_PATCH_EMBED4=0: gather + GEMM + passes, A/B aid)"""
-    return (dst_dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_PATCH_EMBED4", "1") != "0"
+    """mlpk_patch_embed4: Conv2d(3 -> C, k = stride = 4) (+ LayerNorm) in one kernel"""
+    return (dst_dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_patch_embed4_supported(dtype_code(src_dtype), dtype_code(dst_dtype), cin, H, W, C)))
 
 
@@ -598,8 +578,8 @@ def patch_embed4(x, w, bias, out, B, H, W, C, gamma=None, beta=None, eps=1e-5):
 
 
 def stem7_supported(src_dtype, dst_dtype, cin, H, W, pad, C):
-    """mlpk_stem7: Conv2d(3 -> C, k = 7, stride = 4) as a direct convolution (MLPK_STEM7=0: window gather + GEMM, A/B aid)"""
-    return (dst_dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_STEM7", "1") != "0"
+    """mlpk_stem7: Conv2d(3 -> C, k = 7, stride = 4) as a direct convolution"""
+    return (dst_dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_stem7_supported(dtype_code(src_dtype), dtype_code(dst_dtype), cin, H, W, pad, C)))
 
 
@@ -642,8 +622,8 @@ def vip_unpermute(which, z, out, B, H, W, C, seg, ldz):
 
 
 def vip_branch_supported(dtype, H, W, C, seg):
-    """mlpk_vip_branch for BOTH branches of a ViP block (MLPK_VIP_BRANCH=0: the two-kernel path, A/B aid)"""
-    return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_VIP_BRANCH", "1") != "0"
+    """mlpk_vip_branch for BOTH branches of a ViP block"""
+    return (dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_vip_branch_supported(dtype_code(dtype), H, W, C, seg, 0))
             and bool(N.lib().mlpk_vip_branch_supported(dtype_code(dtype), H, W, C, seg, 1)))
 
@@ -681,8 +661,8 @@ def norm_shift_nhwc(x, out_w, out_h, n, h, w, c, kernel_size, mean, rstd, gamma,
 
 
 def as_conv2_supported(dtype, H, W, C, kernel_size):
-    """mlpk_as_conv2 takes the shape (MLPK_ASMLP_FUSED_CONV2=0: the three-kernel sequence, A/B aid)"""
-    return (dtype in (torch.float16, torch.bfloat16) and os.environ.get("MLPK_ASMLP_FUSED_CONV2", "1") != "0"
+    """mlpk_as_conv2 takes the shape"""
+    return (dtype in (torch.float16, torch.bfloat16)
             and bool(N.lib().mlpk_as_conv2_supported(dtype_code(dtype), H, W, C, kernel_size)))
 
 
@@ -690,7 +670,7 @@ def as_conv2(t, y, B, H, W, C, kernel_size, mean, rstd, gamma, beta, w1, b1, w2,
     """y = gelu(conv2_1(shift_W(u)) + b1) + gelu(conv2_2(shift_H(u)) + b2), u = gelu(GroupNorm affine of t): AxialShift's core in one kernel.
     stats = (workspace, name): the kernel also finishes the GroupNorm(1, C) statistics of y (mlpk_as_conv2_stats: one pair per step of
     rows, added in step order inside the kernel -- no statistics pass, no finalize launch); returns (mean, rstd) of y, else None."""
-    if stats is None or os.environ.get("MLPK_ASCONV_STATS", "1") == "0":
+    if stats is None:
         N.check(N.lib().mlpk_as_conv2(dtype_code(t.dtype), ptr(t), ptr(y), B, H, W, C, kernel_size, ptr(mean), ptr(rstd), ptr(gamma), ptr(beta),
                                       ptr(w1), ptr(b1), ptr(w2), ptr(b2), w1.stride(0), stream()), "mlpk_as_conv2")
         return None
@@ -797,7 +777,7 @@ def mixshift_nhwc(x, out, B, H, W, C, shift, ksize, w_lr, b_lr, w_td, b_td, part
     returns (buffer (C / 32, rows, 2), C / 32) as engine.gemm(part=...) does, for finalize_stats; None otherwise (the caller runs row_stats)."""
     g = len(shift)
     arr = ctypes.c_int * g
-    if part is not None and epilogue_stats() and x.dtype != torch.float32:
+    if part is not None and x.dtype != torch.float32:
         nq = N.lib().mlpk_mixshift_stats_planes(dtype_code(x.dtype), B, H, W, C, g, arr(*ksize))
         if nq > 0:
             rows = B * H * W

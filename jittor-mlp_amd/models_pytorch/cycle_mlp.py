@@ -279,7 +279,7 @@ class CycleNet(StochasticDepth, E.EngineModule):
         mean, rstd = stats if stats is not None else layernorm_stats(ws, cur, rows, C, tag=tag + ".ln")
         sh, sw = ws.get(tag + ".sh", (rows, C)), ws.get(tag + ".sw", (rows, C))
         th, tw, tc = ws.get(tag + ".th", (rows, C)), ws.get(tag + ".tw", (rows, C)), ws.get(tag + ".tc", (rows, C))
-        fold = (p + "cf.w") in pk and os.environ.get("MLPK_CYCLE_LN_FOLD") != "0"
+        fold = (p + "cf.w") in pk
         if fold:
             E.cycle_shift_ln(cur, mean, rstd, pk[p + "ln.g"], pk[p + "ln.b"], sh, sw, B, H, W, C, 3, C, C)
         else:

@@ -14,7 +14,6 @@ The patcher (7x7 stride-4 pad-3 conv, :203) and the stage transitions (3x3 strid
 (mlpk_im2col) + GEMM; the channel MLP folds its LayerNorm into fc1; the head folds its LayerNorm into the token mean.
 """
 import contextlib
-import os
 
 import torch
 from torch import nn
@@ -236,7 +235,7 @@ class HireMLP(E.EngineModule):
             return None
         mean, rstd = st if st is not None else layernorm_stats(ws, cur, rows, C, tag="l%d.ln" % li)
         st2 = None                                                                        # statistics of the block's first half, when the combine delivers them
-        fold = cur.dtype != torch.float32 and os.environ.get("MLPK_HIRE_LN_FOLD") != "0"
+        fold = cur.dtype != torch.float32
         if fold:
             # round 5: no stored LayerNorm output -- the gather normalises the vectors it moves, proj_c reads x with the LayerNorm folded in
             E.hire_gather_ln(cur, mean, rstd, pk[p + "ln.g"], pk[p + "ln.b"], a_h, a_w, B, H, W, C, h, w, step, h * C, w * C)
@@ -247,9 +246,8 @@ class HireMLP(E.EngineModule):
         # (short GEMMs of 20-50 us each: two kernels in flight fill the tail of each other's last wave of tiles)
         # one step at a time the w-branch pair runs on a side stream beside the h-branch pair and proj_c; with forwards in flight (no side streams:
         # engine.set_side_streams) the branches' Linears go pairwise into one launch each.  Same box: 9.31 -> 9.14 ms per step in flight with the pairs,
-        # 10.08 -> 10.20 ms one at a time (there the side chain also overlaps proj_c) -- profiles/r06_hire_combine_stats_ab.txt.  MLPK_HIRE_PAIR=0/1 forces.
-        pe = os.environ.get("MLPK_HIRE_PAIR")
-        paired = (pe != "0") if pe is not None else E.side_stream(cur.device) is None
+        # 10.08 -> 10.20 ms one at a time (there the side chain also overlaps proj_c) -- profiles/r06_hire_combine_stats_ab.txt.
+        paired = E.side_stream(cur.device) is None
         chain = E.SideChain(ws, "hire.w", cur.device) if not paired else contextlib.nullcontext()
         if paired:
             # round 6: the two branches' Linears pairwise in ONE launch each (mlpk_gemm_nt_pair: the same tiles, the same bits) -- 20-30 us products,
@@ -268,7 +266,7 @@ class HireMLP(E.EngineModule):
             E.gemm(cur, pk[p + "cf.w"], xn, rows, C, C, bias=pk[p + "cf.b"], ln=(mean, rstd, pk[p + "cf.csum"]), R=cur, res=N.RES_ADD, tag="hire_c")
             if not paired:
                 chain.join()
-            if part != "pre0" and os.environ.get("MLPK_HIRE_COMBINE_STATS") != "0":
+            if part != "pre0":
                 # round 6: the combine delivers the statistics of the rows it writes -- the MLP half's LayerNorm needs no pass over x
                 st2 = (ws.get("l%d.cm.mean" % li, (rows,), torch.float32), ws.get("l%d.cm.rstd" % li, (rows,), torch.float32))
                 E.hire_combine_stats(cur, xn, a_h, a_w, B, H, W, C, h, w, step, h * C, w * C, st2[0], st2[1], eps=blk[1].norm.eps)

@@ -14,7 +14,6 @@ Mapping to kernels:
   * channel fc1/fc2: GEMM with bias+GELU / bias+residual epilogues;
   * head: LN folded into the token mean (mlpk_pool_mean) then one small GEMM.
 """
-import os
 from functools import partial
 
 import torch
@@ -145,7 +144,6 @@ class MLPMixer(E.EngineModule):
                 PreNormResidual(d_model, FeedForward(d_model, d_model * expansion_factor, dropout, chan_last)))
             for _ in range(depth)])
         self._dims = (num_patches, d_model, depth, expansion_factor)
-        self.__dict__["fused_token_mlp"] = os.environ.get("MLPK_NO_FUSED_TOKEN", "0") != "1"
 
     # ---- widths that are not whole 16-byte chunks (round 6; the reference takes any d_model, mlp_mixer.py:46-54) ----
     # The activations carry round_up(C, 8) channels; the extra ones are EXACTLY zero everywhere: zero rows in every weight that produces
@@ -218,7 +216,7 @@ class MLPMixer(E.EngineModule):
             pk[p + "tok.fc2.w"] = E.pack_matrix(tok.fn.net[3].weight, dtype, device, kpad=32)     # (S, 4S_pad)
             pk[p + "tok.fc2.b"] = E.f32(tok.fn.net[3].bias, device)
             S = tok.fn.net[0].weight.shape[1]
-            if self.fused_token_mlp and E.token_mlp_supported(dtype, S, E.round_up(S, 32), tok.fn.net[0].weight.shape[0]):
+            if E.token_mlp_supported(dtype, S, E.round_up(S, 32), tok.fn.net[0].weight.shape[0]):
                 pk[p + "tok.fused"] = E.pack_token_mlp(tok.fn.net[0].weight, tok.fn.net[0].bias, tok.fn.net[3].weight,
                                                        tok.fn.net[3].bias, dtype, device, E.round_up(S, 32),
                                                        t_rows=tok.norm.weight.shape[0])
@@ -240,8 +238,7 @@ class MLPMixer(E.EngineModule):
         for i in range(depth):
             p = "b%d." % i
             fused = pk.get(p + "tok.fused")
-            if (fused is not None and fused[5] in (2, 3) and fused[4] >= 2 and E.token_ln_fused() and C % 128 == 0
-                    and (p + "ch.fc1.csum") in pk and E.epilogue_stats()):
+            if fused is not None and fused[5] in (2, 3) and fused[4] >= 2 and C % 128 == 0 and (p + "ch.fc1.csum") in pk:
                 # the whole token-mixing PreNormResidual in ONE kernel: the LayerNorm + transpose is the token kernel's operand loader
                 # (no xt tensor, x read once); its row statistics come out of the previous block's fc2 epilogue (first block: one pass)
                 w1f, b1f, w2f, b2f, nch, lay = fused
@@ -265,7 +262,7 @@ class MLPMixer(E.EngineModule):
                 # both token-mixing products + GELU + residual in one kernel; the hidden stays in LDS
                 w1f, b1f, w2f, b2f, nch, lay = fused
                 stats = None
-                if C % 128 == 0 and (p + "ch.fc1.csum") in pk and E.epilogue_stats():
+                if C % 128 == 0 and (p + "ch.fc1.csum") in pk:
                     # the statistics of the channel LayerNorm come out of the token kernel's epilogue (no pass over x)
                     part = ws.get("tok.stats", (E.token_mlp_stat_planes(C, lay), rows, 2), torch.float32)
                     E.token_mlp(xt, sp, B * C, S, w1f, b1f, w2f, b2f, nch, x, C, C, stats=part, layout=lay)

@@ -8,7 +8,6 @@ storing through the transpose; a second affine pass; FF as two GEMMs whose secon
 gamma_2 and the residual.
 """
 import contextlib
-import os
 
 import torch
 from torch import nn
@@ -108,7 +107,7 @@ class ResMLP(E.EngineModule):
             pk[p + "fc1.b"] = E.f32(blk.ff.net[0].bias, device)
             pk[p + "fc2.w"] = E.pack_matrix(blk.ff.net[3].weight, dtype, device)
             pk[p + "fc2.b"] = E.f32(blk.ff.net[3].bias, device)
-            if dtype != torch.float32 and os.environ.get("MLPK_RESMLP_FOLD_G2", "1") != "0":
+            if dtype != torch.float32:
                 # round 4: the layer scale gamma_2 (res_mlp.py:49,57) folded into fc2 -- W' = diag(gamma_2) F2, b' = gamma_2 f2 -- so the
                 # product is the plain bias + residual class the generated q4 tile runs (with a per-column scale it fell to the 128 x 128
                 # s3 tile: 34 % of ResMLP-24 at 650 TFLOP/s); one rounding of the scaled weights instead of a scale of the rounded ones

@@ -14,8 +14,6 @@ SwinMLPBlock (swin_mlp.py:63-157) on channel-last tokens (B*H*W, C):
 PatchMerging (:178-212) = 2x2 gather + LayerNorm(4C) folded into the bias-free reduction; head = LayerNorm folded into the
 token mean, then the classifier GEMM.
 """
-import os
-
 import torch
 from torch import nn
 
@@ -222,11 +220,8 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
         dp1 = self._drop_scale(blk.drop_path_rate, B, (Hp // ws) * (Wp // ws) * d, cur.dtype, cur.device)
         dp2 = self._drop_scale(blk.drop_path_rate, B, H * W, cur.dtype, cur.device)
         if dp1 is None and dp2 is None and (p + "sp.fw") in pk and E.swin_spatial_supported(cur.dtype, C, nh, ws):
-            # round 5: the kernel holds whole rows, so it also delivers norm2's statistics of what it writes (no statistics pass;
-            # MLPK_SWIN_SPATIAL_STATS=0: the pass, A/B aid)
-            st2 = None
-            if os.environ.get("MLPK_SWIN_SPATIAL_STATS") != "0":
-                st2 = (ws_.get("l%d.cm.mean" % li, (rows,), torch.float32), ws_.get("l%d.cm.rstd" % li, (rows,), torch.float32))
+            # round 5: the kernel holds whole rows, so it also delivers norm2's statistics of what it writes (no statistics pass)
+            st2 = (ws_.get("l%d.cm.mean" % li, (rows,), torch.float32), ws_.get("l%d.cm.rstd" % li, (rows,), torch.float32))
             E.swin_spatial(cur, B, H, W, C, ws, pad_t, pad_l, Hp, Wp, nh, mean, rstd, pk[p + "n1.g"], pk[p + "n1.b"], pk[p + "sp.fw"], pk[p + "sp.fb"],
                            out_stats=st2)
             got = channel_mlp(ws_, cur, rows, C, pk, p + "ff.", int(C * self.mlp_ratio), tag="l%d.cm" % li, part=(ws_, "l%d.fc2.part" % li), stats=st2)
@@ -266,8 +261,7 @@ class SwinMLP(StochasticDepth, TrainDropout, E.EngineModule):
         # combined from them (mlpk_merge2x2_stats_combine: 1.6 MB instead of a pass over the activations) and the reduction reads `cur` through the 2 x 2
         # window (mlpk_conv_gemm_nhwc, the weight's column blocks in its tap order).  Without st: the gather (a statistics pass over the windows instead
         # measured neutral, profiles/r06_conv_gemm_ab.txt).
-        implicit = st is not None and (p + "wc") in pk and pk[p + "w"].shape[1] == 4 * C and E.conv_gemm_nhwc_supported(cur.dtype, C, 2, 2, 2, 0) and \
-            os.environ.get("MLPK_CONV_GEMM", "1") != "0"
+        implicit = st is not None and (p + "wc") in pk and pk[p + "w"].shape[1] == 4 * C and E.conv_gemm_nhwc_supported(cur.dtype, C, 2, 2, 2, 0)
         if implicit:
             mean = ws_.get("l%d.merge.ln.mean" % li, (B * H2 * W2,), torch.float32)
             rstd = ws_.get("l%d.merge.ln.rstd" % li, (B * H2 * W2,), torch.float32)

@@ -18,7 +18,7 @@ from conftest import ROOT, load_pkg
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
-def test_library_builds_and_exports_every_declared_symbol_at_abi_13():
+def test_library_builds_and_exports_every_declared_symbol_at_abi_14():
     import __graft_entry__ as ge
     ge.build()
     pkg = load_pkg()
@@ -31,7 +31,7 @@ def test_library_builds_and_exports_every_declared_symbol_at_abi_13():
     for name in sorted(declared):
         assert hasattr(lib, name), "libmlpk.so does not export %s" % name
         assert name in pkg._native.PROTOTYPES, "no ctypes prototype for %s" % name
-    assert lib.mlpk_abi_version() == 13
+    assert lib.mlpk_abi_version() == 14
     assert lib.mlpk_gemm_algo_count() >= 4
     bm, bn, th, lds = (ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int())
     assert lib.mlpk_gemm_algo_info(1, bm, bn, th, lds) == 0

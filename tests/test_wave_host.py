@@ -81,14 +81,14 @@ def test_containers_and_cpu_inputs_raise():
             mod(x)
 
 
-def test_wave_patm_declared_and_exported_at_abi_13():
+def test_wave_patm_declared_and_exported_at_abi_14():
     N = load_pkg()._native
     assert "mlpk_wave_patm" in N.PROTOTYPES and "mlpk_wave_patm_supported" in N.PROTOTYPES
     with open(os.path.join(ROOT, "include", "mlpk.h")) as f:
         h = f.read()
     assert "int mlpk_wave_patm(" in h and "int mlpk_wave_patm_supported(" in h
     lib = N.lib()                                           # every PROTOTYPES entry resolved, ABI checked
-    assert lib.mlpk_abi_version() == 13
+    assert lib.mlpk_abi_version() == 14
 
 
 def test_wave_patm_argument_errors():

@@ -66,7 +66,6 @@ def loops():
     for name, M, dbg in (("real plan 50176 rows (588 tiles)", 50176, 0), ("256-row tiles only, 50176 rows", 50176, 16),
                          ("1 round: 255 tiles", 21760, 16), ("2 rounds: 510 tiles", 43520, 16), ("3 rounds: 765 tiles", 65280, 16),
                          ("1 round of 192-row tiles", 85 * 192, 0)):
-        os.environ.pop("MLPK_P8_FORCE_NI", None)
         for nbuf, label in ((1, "warm"), (max(2, int(np.ceil(700e6 / (M * K * 2)))), "cold")):
             f = case(M, dbg, nbuf)
             gp.loop("%-34s %s x%d" % (name, label, nbuf), f, 2.0 * M * Nn * K)
