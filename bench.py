@@ -13,13 +13,17 @@ reference's compare.py:149-158: warm-up, device sync, K timed forwards, device s
 With --dump-outputs DIR, rank 0 also writes the logits the last timed step returned as DIR/logits.npy (float32; inputs and weights
 are seeded, so two builds run with the same arguments can be compared output for output).
 
-Rank 0 prints ONE JSON line with the contract fields plus
-  roofline     -- the dominant kernel (channel-MLP GEMM, 79 % of the flops): algorithmic
-                  2*M*N*K per launch / HIP-event time of those launches inside the timed region,
-                  against the gfx950 dense bf16 MFMA peak (2.5 PFLOP/s);
-  cpu_baseline -- the CPU oracle (oracle/, a port of the reference forward) timed on this host,
-                  best of a thread sweep, on a bounded sample (the benched model, fp32, bs=8) plus
-                  BASELINE configs[0] (Mixer-S/16, bs=8, fp32) under "config1"; N=1 only.
+Rank 0 prints ONE JSON line with the contract fields.  A plain run does only what that line needs: set-up, the W warm-up steps,
+the K timed steps, the dump.  With --full the same run also takes the measurements that need passes of their own, around
+the same warm-up and timed steps, and adds them to the line:
+  single_stream      -- the same steps strictly one after the other on one stream (when --streams > 1, the default);
+  kernels, roofline  -- the dominant kernel (channel-MLP GEMM, 79 % of the flops): algorithmic 2*M*N*K per launch /
+                        HIP-event time of those launches in a short serial pass of their own, against the gfx950
+                        dense bf16 MFMA peak (2.5 PFLOP/s);
+  fp32_input_variant -- fp32 images in, model.set_compute_dtype(): the drop-in contract's own path; N=1 only;
+  cpu_baseline       -- the CPU oracle (oracle/, a port of the reference forward) timed on this host, best of a
+                        thread sweep, on a bounded sample (the benched model, fp32, bs=8) plus BASELINE configs[0]
+                        (Mixer-S/16, bs=8, fp32) under "config1"; N=1 only.
 """
 import argparse
 import importlib
@@ -273,9 +277,12 @@ def main():
     ap.add_argument("--gemm-plan", default="auto", choices=["auto", "mixed", "whole"],
                     help="tile heights of the persistent GEMM: mixed = shortest single launch, whole = least total CU time (engine.set_gemm_plan); "
                          "auto = whole when several steps are in flight, mixed otherwise")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the fp32-input variant line (profiling runs count forwards)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes passes of its own beside the warm-up and timed steps: single_stream, kernels / roofline, "
+                         "fp32_input_variant, cpu_baseline (about 30 s more).  Off: only the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip kernels / roofline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the fp32-input variant line")
     ap.add_argument("--algo", default="", help="tag=algo[,tag=algo] GEMM tile overrides (tuning)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl == RCCL on ROCm; gloo only for "
                     "exercising the multi-process path on a single-GPU box together with --share-device)")
@@ -363,7 +370,7 @@ def main():
         """Per-kernel durations for `roofline`: HIP events around the channel-MLP GEMM launches (on the stream they are launched on) in a
         SEPARATE short pass of whole steps, one step at a time on one stream -- same process, same resident batch -- so that the headline
         loop carries no event records at all (round-4 review: 24 pairs per step sat inside it)"""
-        if args.no_kernel_timing:
+        if args.no_kernel_timing or not args.full:
             return None, 0
         timer = E.KernelTimer()
         n = max(2, min(args.steps, 6))
@@ -382,7 +389,12 @@ def main():
         # flight the chip sits 4 % lower at the power cap and a kernel shares the CUs with the other step: not a statement about the kernel)
         serial = None
         timer, timing_steps, timing_where = None, 0, ""
-        if side is not None:
+        if side is not None and not args.full:
+            # set-up: the first forward packs the weights with kernels on the stream it is called on, and the pack cache keeps no event
+            # for a second stream to wait on -- pack on this stream and finish, before the in-flight streams read the packs
+            runner(x)
+            torch.cuda.synchronize()
+        if side is not None and args.full:
             plan_in_flight, side_in_flight = E.GEMM_PLAN_WHOLE, E.SIDE_STREAMS     # the serial passes run the serial regime's own GEMM plan and side streams
             if args.gemm_plan == "auto":
                 E.set_gemm_plan(False)
@@ -425,7 +437,7 @@ def main():
         if side is None:
             timer, timing_steps = kernel_timing_pass()
             timing_where = "%d extra steps straight after the %d timed ones" % (timing_steps, args.steps)
-        else:
+        elif args.full:
             serial["bits_equal_to_timed_steps"] = bool(torch.equal(out1, out))
             del out1
             if args.gemm_plan == "auto":
@@ -438,7 +450,7 @@ def main():
         # set_compute_dtype: the image is converted while the patches are gathered and the logits come back in fp32.  The headline above
         # keeps the batch resident in the compute dtype; this variant line times the contract itself on the same model (N = 1 only).
         fp32_variant = None
-        if world == 1 and cd != torch.float32 and hasattr(model, "set_compute_dtype") and not args.no_variants:
+        if world == 1 and cd != torch.float32 and hasattr(model, "set_compute_dtype") and args.full and not args.no_variants:
             x32 = x.float()
             model.set_compute_dtype(cd)
             for _ in range(3):
@@ -517,7 +529,7 @@ def main():
                     line["roofline"]["frac_behind_timed_region"] = round(fa / line["roofline"]["peak"], 4)
                     line["roofline"]["frac_behind_timed_region_note"] = ("the same serial pass repeated straight after the timed region: with two steps in flight "
                                                                          "the chip sits lower at its power cap and the pass inherits that state")
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = run_cpu_baseline(args.model, kwargs, ctor_name, pkg)
             except Exception as e:      # a baseline failure must not discard the measured GPU line

@@ -141,3 +141,38 @@ def test_two_forwards_in_flight_give_the_serial_bits():
         assert not pkg.engine.GEMM_PLAN_WHOLE and pkg.engine.SIDE_STREAMS
         for (out, _), x in zip(got, hx):
             assert torch.equal(out, hire(x))                     # (one call after the other, on its side stream again)
+
+
+def test_bench_plain_run_is_the_headline_alone_and_full_adds_the_rest(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` sets up, warms up, times its N steps and prints the contract line, nothing else;
+    `--full` takes the other measurements around the SAME warm-up and timed steps.  So the plain line carries none of the extra
+    blocks and the full line carries them (--no-cpu-baseline: the CPU sweep needs no GPU); one step at a time (--streams 1, where
+    repeated forwards return the same bits) the two runs dump bit-equal logits."""
+    import json
+    import subprocess
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    extras = ("single_stream", "fp32_input_variant", "kernels", "roofline", "cpu_baseline")
+
+    def run(name, opts):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / name)] + opts, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        a = np.load(tmp_path / name / "logits.npy")
+        assert a.dtype == np.float32 and a.shape == (256, 1000) and np.isfinite(a).all()
+        return json.loads(lines[0]), a
+
+    plain, _ = run("plain", [])
+    full, _ = run("full", ["--full", "--no-cpu-baseline"])
+    assert not [k for k in extras if k in plain]
+    assert all(k in full for k in ("single_stream", "fp32_input_variant", "kernels", "roofline")) and "cpu_baseline" not in full
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus", "config"):
+        assert plain[k] == full[k], k
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 2 and plain["warmup"] == 1
+    plain1, a1 = run("plain1", ["--streams", "1"])
+    full1, b1 = run("full1", ["--streams", "1", "--full", "--no-cpu-baseline"])
+    assert not [k for k in extras if k in plain1]
+    assert all(k in full1 for k in ("fp32_input_variant", "kernels", "roofline")) and "single_stream" not in full1
+    assert np.array_equal(a1, b1)

@@ -96,6 +96,22 @@ def test_bench_launches_itself_for_n_ranks():
     assert r1.returncode == 0 and json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
 
 
+def test_bench_takes_full_beside_the_plain_run():
+    """`--full` (the measurements beside the headline: off by default) is an option of every run; the stub forward has nothing of that
+    kind, so both forms print the same contract fields."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    lines = []
+    for extra in ([], ["--full"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--cpu-stub"] + extra,
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0]))
+    assert sorted(lines[0]) == sorted(lines[1])
+    assert all(k in lines[0] for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+
+
 def test_bench_dumps_the_last_timed_step(tmp_path):
     """`--dump-outputs DIR` writes the logits the last timed step returned (gathered over the ranks) as DIR/logits.npy in float32;
     `--steps` below 1 is refused rather than timing nothing."""
