@@ -890,6 +890,37 @@ class EngineModule(torch.nn.Module):
             stack.extend(c for c in m._modules.values() if c is not None)
         return tuple(out)
 
+    def invalidate_caches(self):
+        """Drop every cache derived from the parameters: the packed weights and workspaces of this module and of every EngineModule
+        below it, and the train path's packed copies (autograd._PACKS) of its parameters.  The next forward packs again.
+        `_param_stamp` sees a parameter or buffer that was replaced or written through torch's version counter (load_state_dict,
+        optimizers, in-place ops under no_grad, `p.data = t`, `.to()` / `.half()`); it cannot see a write that bypasses the counter
+        without reading device memory -- `p.data.mul_(2)`, `p.data -= lr * g`, a collective on `p.data`, a kernel given `p.data_ptr()`:
+        call this after such a write.  Returns self."""
+        from . import autograd
+        ids, stack, seen = set(), [self], set()
+        while stack:
+            m = stack.pop()
+            if id(m) in seen:
+                continue
+            seen.add(id(m))
+            if isinstance(m, EngineModule):
+                m._packs.clear()
+                m._spaces.clear()
+            ids.update(id(t) for t in m._parameters.values() if t is not None)
+            ids.update(id(t) for t in m._buffers.values() if t is not None)
+            stack.extend(c for c in m._modules.values() if c is not None)
+        for key in [k for k in autograd._PACKS if k[0] in ids]:
+            del autograd._PACKS[key]
+        return self
+
+    def __getstate__(self):
+        # copy.deepcopy and pickle (torch.save(model)) take the module without its device caches: a copy that shared or duplicated the
+        # workspaces (and their torch.cuda.Events, which do not pickle) would be wrong or wasteful; the copy packs at its first forward
+        state = dict(super().__getstate__())
+        state["_packs"], state["_spaces"] = {}, {}
+        return state
+
     def _get_pack(self, dtype, device):
         key = (dtype, str(device))
         stamp = self._param_stamp()
