@@ -894,20 +894,41 @@ extern "C" int mlpk_norm_apply(const mlpk_norm_desc* d, void* stream) {
     if ((uintptr_t)d->x & 15) return MLPK_EALIGN;
     const int sg = d->stat_group > 0 ? d->stat_group : 1;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // every argument check of every requested output comes before the first launch: a refused call writes nothing
+    if (d->out_rm && (d->ld_rm % 8 || d->ld_rm < d->C || ((uintptr_t)d->out_rm & 15))) return MLPK_ESHAPE;
+    if (d->out_tt && (d->S <= 0 || d->rows % d->S || d->ld_tt % 8 || d->ld_tt < d->S || ((uintptr_t)d->out_tt & 15))) return MLPK_ESHAPE;
+    if (!d->out_tt && d->out_rm && d->rows > 0x7fffffffLL) return MLPK_ESHAPE;
+    bool fast[2] = {false, false};       // per ViP output: the 16-byte kernel or the generic one, and its dynamic LDS bytes
+    size_t lds[2] = {0, 0};
+    for (int which = 0; which < 2; ++which) {
+        const void* out = which == 0 ? d->out_ph : d->out_pw;
+        if (!out) continue;
+        if (d->H <= 0 || d->W <= 0 || d->seg <= 0 || d->C % d->seg) return MLPK_ESHAPE;
+        if (d->rows % ((int64_t)d->H * d->W)) return MLPK_ESHAPE;
+        const int L = which == 0 ? d->H : d->W;
+        if (d->ld_p < L * d->seg) return MLPK_ESHAPE;
+        if (sg != 1) return MLPK_EMODE;
+        const float* sums = which == 0 ? d->sum_ph : d->sum_pw;
+        if (sums && d->ld_sum < (which == 0 ? d->W : d->H) * d->seg) return MLPK_ESHAPE;
+        const int es_ = esize(d->dtype);
+        const size_t lds_fast = (size_t)(d->C / d->seg) * ((size_t)d->ld_p * es_ + 32) + (size_t)2 * d->C * 4;
+        fast[which] = d->seg % 4 == 0 && d->C % 8 == 0 && d->ld_p % 8 == 0 && (d->ld_p * es_) % 16 == 0 &&
+                      ((uintptr_t)out & 15) == 0 && lds_fast <= 160 * 1024;
+        lds[which] = fast[which] ? lds_fast : (size_t)L * d->C * es_;
+        if (!fast[which] && sums) return MLPK_EMODE;       // the by-product sums exist in the 16-byte fast path only
+        if (lds[which] > 160 * 1024) return MLPK_ESHAPE;
+    }
     if (d->out_rm || d->out_tt) {
         NormArgs a;
         a.x = d->x; a.mean = d->mean; a.rstd = d->rstd; a.gamma = d->gamma; a.beta = d->beta;
         a.out_rm = d->out_rm; a.out_tt = d->out_tt; a.rows = d->rows; a.C = d->C; a.ldx = d->ldx;
         a.stat_group = sg; a.act = d->act; a.ld_rm = d->ld_rm; a.ld_tt = d->ld_tt;
-        if (d->out_rm && (d->ld_rm % 8 || d->ld_rm < d->C || ((uintptr_t)d->out_rm & 15))) return MLPK_ESHAPE;
         int S = d->S, nimg;
         if (d->out_tt) {
-            if (S <= 0 || d->rows % S || d->ld_tt % 8 || d->ld_tt < S || ((uintptr_t)d->out_tt & 15)) return MLPK_ESHAPE;
             nimg = (int)(d->rows / S);
             a.s_tiles = (d->ld_tt + 63) / 64;
         } else {
             // no transposed output: treat all rows as one "image" so tiles simply walk the rows
-            if (d->rows > 0x7fffffffLL) return MLPK_ESHAPE;
             S = (int)d->rows;
             nimg = 1;
             a.s_tiles = (S + 63) / 64;
@@ -920,42 +941,29 @@ extern "C" int mlpk_norm_apply(const mlpk_norm_desc* d, void* stream) {
     for (int which = 0; which < 2; ++which) {
         void* out = which == 0 ? d->out_ph : d->out_pw;
         if (!out) continue;
-        if (d->H <= 0 || d->W <= 0 || d->seg <= 0 || d->C % d->seg) return MLPK_ESHAPE;
-        if (d->rows % ((int64_t)d->H * d->W)) return MLPK_ESHAPE;
-        const int L = which == 0 ? d->H : d->W;
-        if (d->ld_p < L * d->seg) return MLPK_ESHAPE;
-        if (sg != 1) return MLPK_EMODE;
         VipArgs a;
         a.x = d->x; a.mean = d->mean; a.rstd = d->rstd; a.gamma = d->gamma; a.beta = d->beta; a.out = out;
         a.B = (int)(d->rows / ((int64_t)d->H * d->W)); a.H = d->H; a.W = d->W; a.C = d->C; a.seg = d->seg;
         a.ldx = d->ldx; a.ld_p = d->ld_p; a.which = which; a.act = d->act;
         a.sums = which == 0 ? d->sum_ph : d->sum_pw;
         a.ld_sum = d->ld_sum;
-        if (a.sums && d->ld_sum < (which == 0 ? d->W : d->H) * d->seg) return MLPK_ESHAPE;
         const unsigned grid = (unsigned)(a.B * (which == 0 ? d->W : d->H));
-        const int es_ = esize(d->dtype);
-        const size_t lds_fast = (size_t)(d->C / d->seg) * ((size_t)d->ld_p * es_ + 32) + (size_t)2 * d->C * 4;
-        const bool fast = d->seg % 4 == 0 && d->C % 8 == 0 && d->ld_p % 8 == 0 && (d->ld_p * es_) % 16 == 0 &&
-                          ((uintptr_t)out & 15) == 0 && lds_fast <= 160 * 1024;
-        if (fast) {
+        const size_t bytes = lds[which];
+        if (fast[which]) {
             DISPATCH_DTYPE(d->dtype, {
                 auto k = vip_permute_fast_kernel<T>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_fast);
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
                 if (e != hipSuccess) return (int)e;
-                hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds_fast, s, a);
+                hipLaunchKernelGGL(k, dim3(grid), dim3(256), bytes, s, a);
             });
-            MLPK_LAUNCH_CHECK();
-            continue;
+        } else {
+            DISPATCH_DTYPE(d->dtype, {
+                auto k = vip_permute_kernel<T>;
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                if (e != hipSuccess) return (int)e;
+                hipLaunchKernelGGL(k, dim3(grid), dim3(256), bytes, s, a);
+            });
         }
-        if (a.sums) return MLPK_EMODE;                   // the by-product sums exist in the 16-byte fast path only
-        const size_t lds = (size_t)L * d->C * esize(d->dtype);
-        if (lds > 160 * 1024) return MLPK_ESHAPE;
-        DISPATCH_DTYPE(d->dtype, {
-            auto k = vip_permute_kernel<T>;
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, a);
-        });
         MLPK_LAUNCH_CHECK();
     }
     return 0;
