@@ -147,16 +147,12 @@ typedef struct mlpk_gemm_desc {
     int32_t algo;         /* 0 auto; otherwise a tile-config id, see mlpk_gemm_algo_count */
     int32_t ln_group;     /* rows that share one folded statistic: 0 / 1 = LayerNorm (one per row); H*W = GroupNorm(1, C) on channel-last
                              rows (one per sample, as_mlp.py:343-344) */
-    int32_t reserved;     /* 0.  Tuning bits (A/B runs and tests only); bits 8 and up are ignored.  Results are bit-identical with
-                             every combination of 16, 32, 64 and 128:
+    int32_t reserved;     /* 0.  Plan bits (A/B runs and tests only); results are bit-identical with every combination of them:
                                16 = persistent tile (algo 14): 256-row tiles only (no mixed tile heights)
                                32 = persistent tile: non-temporal stores in the direct epilogue
                                64 = persistent tile: LDS-staged epilogue
                               128 = persistent tile and generated tile (algo 15): a single column group
-                             Measurement bits of the hand-written tiles (algo 1 .. 14), results WRONG by construction:
-                                1 = no main loop, 2 = no stores, 4 = no epilogue (in the tiles that implement them),
-                                8 = per-workgroup cycle stamps into R (register-staged and s3 tiles); in -DMLPK_P8_PROF builds
-                                    also the persistent tile's per-workgroup cycle sums into `workspace` */
+                             Every other bit is ignored. */
     /* Unused since ABI 5 (mlpk_gemm_workspace_bytes() == 0): every tile is computed by one workgroup, in one K order,
        so results never depend on the batch a row is computed in.  Kept so that descriptors stay layout-compatible. */
     void* workspace;

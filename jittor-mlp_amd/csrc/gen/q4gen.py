@@ -27,18 +27,12 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from isa import A, F, H, S, V, Asm, Neg, Reg, h2bits  # noqa: E402
 
-# the 16-bit GELU polynomials of mlpk_common.h (MLPK_GELUP_*) by storage type.  f16: (scale, Horner coefficients) of the centred form
-# t = clamp(x * scale, -sqrt2, sqrt2), u = t * t - 1; bf16: (clamp, coefficients) of the raw form t = clamp(x, -clamp, clamp), u = t * t
+# the f16 GELU polynomial of mlpk_common.h (MLPK_GELUP_*): (scale, Horner coefficients) of the centred form
+# t = clamp(x * scale, -sqrt2, sqrt2), u = t * t - 1
 GELU = {"f16": (0.314269681, [0.00260713836, -0.00718860654, 0.00979797821, -0.0172248576, 0.0355015062, -0.0601866171, 0.090279378,
-                              -0.127707109, 0.174028099, -0.245624334, 0.499268919]),
-        "bf16": (4.0, [-1.58078628e-09, 1.21711111e-07, -4.10086659e-06, 8.06673925e-05, -0.00104820437, 0.00966487452, -0.0661753789,
-                       0.39884752])}
-GELU_RAW = {"f16": False, "bf16": True}
-# round 4, bf16 grade: gelu(x) = x / (1 + 2^(x (k0 + k1 |x| + k2 x^2)))  (mlpk_common.h MLPK_GELUS_K*, tools/fit_gelu_sig.py).  The generated
-# kernels no longer emit it, nor the bf16 polynomial above: those constants stay as the record of the header's numbers.
-GELU_SIG = {"bf16": (-2.28684449, -0.0305621661, -0.0905431807)}
-# round 5: the bf16 form is "h2b" -- Phi in packed f16 (GELU_H2 below), the product in fp32 on the unrounded x (mlpk_common.h gelu_h2b_f).
-# (The logistic and polynomial bf16 forms were generation-time A/B switches until ABI 14: profiles/r05_issue_slots_packed_gelu.txt.)
+                              -0.127707109, 0.174028099, -0.245624334, 0.499268919])}
+# the bf16 form is "h2b" -- Phi in packed f16 (GELU_H2 below), the product in fp32 on the unrounded x (mlpk_common.h gelu_h2b_f).
+# (A logistic and a polynomial bf16 form were measured against it and not kept: profiles/r05_gelu_h2b_ab.txt, r05_issue_slots_packed_gelu.txt.)
 GELU_FORM = {"f16": "poly", "bf16": "h2b"}
 
 

@@ -78,7 +78,6 @@ class T4:
         self.mfma2 = "v_mfma_f32_32x32x16_f16" if h2 else self.mfma          # the second product
         self.cvt = "v_cvt_pk_bf16_f32" if dtype == "bf16" else "v_cvt_pk_f16_f32"
         self.dot = "v_dot2c_f32_bf16" if dtype == "bf16" else "v_dot2c_f32_f16"
-        self.coefs = GELU[dtype][1]
         self.a = Asm()
         self.build()
 
@@ -205,7 +204,6 @@ class T4:
         for rb in range(2):
             for grp in range(4):                      # accumulator registers 4 grp .. 4 grp + 3
                 x = [self.xg[par_in][rb][4 * grp + r] for r in range(4)]
-                scale, c = GELU[self.dtype]
                 kk, e0 = grp >> 1, 4 * (grp & 1)
                 hreg = self.h[par_out][rb][kk]
                 if self.h2:
@@ -215,6 +213,7 @@ class T4:
                 if self.h2b:
                     h2b_gelu_ops(E, x, self.v_hp, T[0:2], U[0:2], Q[0:2], [self.v_c0] + self.v_hc, self.s_k0, self.s_k1, self.v_nz)
                 else:                                  # (f16: the centred polynomial)
+                    scale, c = GELU[self.dtype]
                     for r in range(4):
                         E("v_mul_f32", T[r], F(scale), x[r])
                     for r in range(4):
@@ -650,7 +649,7 @@ class T4:
             a("s_mov_b32", self.s_k1, h2bits(GELU_H2["coefs"][6]))
             a("v_mov_b32", self.v_nz, 0x80000000)
         else:
-            a("v_mov_b32", self.v_c0, F(self.coefs[0]))
+            a("v_mov_b32", self.v_c0, F(GELU[self.dtype][1][0]))
         a("s_mov_b32", self.s_mask[0], -1)
         a("s_mov_b32", self.s_mask[1], 0)
         a("s_lshl_b32", self.s_wv1k, self.s_wave, 10)

@@ -106,21 +106,15 @@ template <int KS1, int NB> struct CmGeo {
     static constexpr int LDS = B2 + 16 * NB * 4;
 };
 
-// Round 6 (profiles/r06_chanmlp_variants.txt; -DCM_WGS2=0 / -DCM_PREFETCH=0 rebuild the round-5 kernel for A/B):
+// Round 6 (profiles/r06_chanmlp_variants.txt):
 //   * the residual rows ARE the operand rows in every pre-norm residual block (R == x): read once (template SAME);
 //   * the next tile's rows are requested straight after the tile's last fc1 -- their registers are free from there on -- and travel
 //     under the last GELU, fc2 and the epilogue instead of after them;
 //   * two workgroups per CU where their rings and registers fit twice (C <= 96): one's tile hand-over and barrier waits are filled
 //     by the other's iterations.  802816 x 96: 253 -> 224 us, x 64: 151 -> 127, 200704 x 128: 114 -> 101, x 192: 197 -> 191.
-#ifndef CM_WGS2
-#define CM_WGS2 1
-#endif
-#ifndef CM_PREFETCH
-#define CM_PREFETCH 1
-#endif
 // (f16 at C = 96: its longer GELU polynomial does not fit 128 registers without spilling -- one workgroup per CU there)
 template <typename T, int KS1, bool SAME> struct CmWgs {
-    static constexpr int value = (CM_WGS2 && SAME && (KS1 <= 2 || (KS1 == 3 && dtype_of<T>::value == MLPK_BF16))) ? 2 : 1;
+    static constexpr int value = (SAME && (KS1 <= 2 || (KS1 == 3 && dtype_of<T>::value == MLPK_BF16))) ? 2 : 1;
 };
 
 // SAME: the residual rows ARE the operand rows (R == x, the pre-norm residual block of every family): read once
@@ -131,7 +125,7 @@ __global__ void __launch_bounds__(512, (2 * CmWgs<T, KS1, SAME>::value)) chan_ml
     constexpr int C = 16 * NB;
     // the next tile's rows requested straight after the tile's last fc1 (a residual that is not the operand doubles the registers
     // requested ahead: the wide widths would spill)
-    constexpr bool PRE = CM_PREFETCH && (SAME || KS1 <= 4);
+    constexpr bool PRE = SAME || KS1 <= 4;
     static_assert(NB == 2 * KS1, "C = 32 KS1 = 16 NB");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr_t;

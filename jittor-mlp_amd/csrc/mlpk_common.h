@@ -45,56 +45,26 @@ __device__ __forceinline__ float gelu_f(float x) {
     return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752440f));
 }
 
-// GELU for 16-bit outputs, division-free:
-//   gelu(x) = x * Phi(x),  Phi(x) ~= 0.5 + t * Q(t^2 - 1),  t = clamp(x * sqrt2 / 4.5, -sqrt2, sqrt2)
-// Q = degree-10 polynomial in u = t^2 - 1 in [-1, 1] (weighted minimax fit of the error of Phi, tools/fit_gelu_poly.py; sum |c| =
-// 1.27, so fp32 Horner is well conditioned).  16 VALU instructions per PAIR of elements (everything but the clamp pairs into
-// v_pk_* ops) and no transcendental; the form it replaces -- erf by Abramowitz & Stegun 7.1.28, 1 - (1 + a1 z + .. + a6 z^6)^-16 --
-// took 19 + 2 v_rcp_f32 per pair, and the kernels that evaluate GELU are bound by VALU instruction count (the fused
-// token-mixing kernel: profiles/r02_token_mlp_ablation.txt; the fc1 epilogue of the channel MLP).
+// GELU for 16-bit outputs, division-free and without a transcendental: the kernels that evaluate it are bound by VALU instruction count
+// (the fused token-mixing kernel: profiles/r02_token_mlp_ablation.txt; the fc1 epilogue of the channel MLP).  float outputs keep gelu_f.
+// Two grades, by storage type of the result (a logistic and a raw-variable polynomial bf16 grade were measured and not kept:
+// profiles/r05_gelu_h2b_ab.txt, profiles/r05_gelu_accuracy_ab.txt).
+//
+// f16 -- the centred polynomial (tools/fit_gelu_poly.py 4.5 11):
+//         gelu(x) = x * Phi(x),  Phi(x) ~= 0.5 + t * Q(t^2 - 1),  t = clamp(x * sqrt2 / 4.5, -sqrt2, sqrt2)
+// Q = degree-10 polynomial in u = t^2 - 1 in [-1, 1] (weighted minimax fit of the error of Phi; sum |c| = 1.27, so fp32 Horner is well
+// conditioned).  16 VALU instructions per PAIR of elements (everything but the clamp pairs into v_pk_* ops).
 // |Phi error| <= 2.7e-6 everywhere (|x| > 4.5 clamps to Phi(4.5) = 1 - 3.4e-6), |gelu error| <= 3.7e-6 on |x| <= 4.5: 60x below
 // half an ulp of f16 at that magnitude; checked in fp32 emulation by tests/test_host_cpu.py against the coefficients HERE.
-// float outputs keep gelu_f.
-// Two grades (tools/fit_gelu_poly.py A K), by storage type of the result:
-//   f16 : A = 4.5, 11 coefficients -- |Phi error| <= 2.7e-6, |gelu error| <= 3.7e-6 on |x| <= 4.5 (60x below half an ulp of f16)
-//   bf16: A = 4.0,  8 coefficients -- |Phi error| <= 5.3e-5, |gelu error| <= 9e-5 on |x| <= 4 (half an ulp of bf16 is 2^-9 relative:
-//         the polynomial error stays below the rounding of every result above 0.04 in magnitude); three fewer fma per element in the
-//         kernels whose epilogues are bound by VALU issue (round 3: the q4 GEMM's fillers, the token-mixing kernel).  At this grade the
-//         SAME fit is evaluated in the variable the kernels have at hand, without the scaling multiply in front of the clamp:
-//             Phi(x) ~= 0.5 + t * R(t * t),  t = clamp(x, -4, 4)          (tools/fit_gelu_poly.py 4.0 8 raw)
-//         -- R's coefficients sum to 81 in the variable (t/4)^2, i.e. ~5e-6 of fp32 cancellation, nothing against 9e-5; the f16
-//         grade (sum 500+) keeps the centred variable.  11 operations per element instead of 12.
 #define MLPK_GELUP_SCALE 0.314269681f
 #define MLPK_GELUP_COEFS {0.00260713836f, -0.00718860654f, 0.00979797821f, -0.0172248576f, 0.0355015062f, -0.0601866171f, 0.090279378f, -0.127707109f, 0.174028099f, -0.245624334f, 0.499268919f}
-#define MLPK_GELUP_CLAMP_BF16 4.0f
-#define MLPK_GELUP_COEFS_BF16 {-1.58078628e-09f, 1.21711111e-07f, -4.10086659e-06f, 8.06673925e-05f, -0.00104820437f, 0.00966487452f, -0.0661753789f, 0.39884752f}
-// Round 4 -- the logistic bf16 grade (round 5: behind -DMLPK_GELU_BF16_SIG; the polynomial above behind -DMLPK_GELU_BF16_POLY; default: "h2b" below):
-//         gelu(x) = x * Phi(x),   Phi(x) ~= 1 / (1 + 2^(x * (K0 + K1 |x| + K2 x^2)))          (tools/fit_gelu_sig.py)
-// a logistic with a cubic exponent, odd in x.  SEVEN instructions per element -- fma, fma (|x| is a source modifier), mul, v_exp_f32,
-// add, v_rcp_f32, mul -- against eleven: the epilogues that carry a GELU are bound by the number of instructions one wave can issue
-// behind its MFMAs (the q4 GEMM's fillers, the fused token-mixing kernel: 6.6 VALU operations per MFMA where 5 are free), and a
-// transcendental costs about two cycles more than a plain operation there (tools/ubench/q4_slots.py exp* / alt_* / target* rows).
-// |gelu error| <= 1.4e-4 for EVERY finite x (|Phi error| <= 3.7e-4 near 0 where gelu itself is small, <= 7e-5 beyond |x| = 2); the
-// exponent's leading coefficient has the sign of K0, so Phi -> 0 / 1 and gelu -> -0 / x in the tails without a clamp -- the clamped
-// polynomial's error grew like 5e-5 |x| beyond its interval (gelu(-1000) = -0.05).  Checked in emulated fp32 by tests/test_host_cpu.py.
-#define MLPK_GELUS_K0 -2.28684449f
-#define MLPK_GELUS_K1 -0.0305621661f
-#define MLPK_GELUS_K2 -0.0905431807f
-__device__ __forceinline__ float gelu_sig_f(float x) {
-    const float a = __builtin_fabsf(x);
-    float q = __builtin_fmaf(a, MLPK_GELUS_K2, MLPK_GELUS_K1);
-    q = __builtin_fmaf(a, q, MLPK_GELUS_K0);
-    const float e = __builtin_amdgcn_exp2f(x * q);
-    return x * __builtin_amdgcn_rcpf(1.0f + e);
-}
 
-// Round 5 -- the bf16 grade every kernel evaluates now ("h2b"; -DMLPK_GELU_BF16_SIG keeps the logistic form above, -DMLPK_GELU_BF16_POLY the
-// polynomial, for A/B builds):  gelu(x) = x * Phi(h),  h = f16(x) (nearest-even),  Phi in PACKED f16 -- two elements per instruction:
+// bf16 -- "h2b":  gelu(x) = x * Phi(h),  h = f16(x) (nearest-even),  Phi in PACKED f16 -- two elements per instruction:
 //         t = h * S;  u = t * t - 1;  Phi = clamp01(0.5 + t * Q(u)),  Q = 7 coefficients by Horner            (tools/fit_gelu_h2.py)
 // -- and the product in fp32 on the unrounded x (v_fma_mix_f32 reads the f16 half as an fp32 source).  Per PAIR: 1 convert + 9 packed + 2
-// mixed = 12 plain instructions, none transcendental, against 14 of which four are quarter-rate (v_exp_f32 / v_rcp_f32): in the epilogues that
-// are bound by VALU time (gMLP's channel_proj1, the narrow channel MLPs) a transcendental costs four plain issue cycles, in the q4 GEMM's
-// filler stream two (profiles/r05_issue_slots_packed_gelu.txt: the fc1 loop 39.45 -> 37.71 cycles per MFMA).  No operand clamp: the fit's
+// mixed = 12 plain instructions: in the epilogues that are bound by VALU time (gMLP's channel_proj1, the narrow channel MLPs) a
+// transcendental costs four plain issue cycles, in the q4 GEMM's filler stream two (profiles/r05_issue_slots_packed_gelu.txt: the fc1
+// loop 39.45 -> 37.71 cycles per MFMA).  No operand clamp: the fit's
 // leading coefficient is positive, so beyond |x| = 4 the polynomial runs off in the direction the result clamp wants (h = +-inf included:
 // every intermediate is +-inf of the right sign, never inf - inf), and x itself stays fp32, so gelu(-1e6) = -1e6 * 0 = -0.
 // |gelu error| <= 9e-4 |x| on |x| >= 0.25 (half an ulp of bf16 is 2e-3 |x|), <= 1.7e-4 below; rms 1.2e-4 .. 3.5e-4 for x ~ N(0, 0.5 .. 2): +1 .. 3 %
@@ -149,37 +119,31 @@ template <int N> __device__ __forceinline__ void gelu_h2_phi_n(unsigned (&h)[N])
     asm volatile("v_pk_fma_f16 %0, %1, %2, 0.5 op_sel_hi:[1,1,0] clamp\n\ts_nop 0" : "=v"(h[N - 1]) : "v"(t[N - 1]), "v"(q[N - 1]));
 }
 
-// gelu on N independent pairs with the N dependency chains interleaved step by step: a single wave running ONE
+// the f16 grade on N independent pairs with the N dependency chains interleaved step by step: a single wave running ONE
 // chain is latency-bound (each v_pk op waits for its predecessor); N = 4 keeps the VALU issuing back to back.
-// RAW: the bf16 grade's form (t = clamp(x, -scale, scale), u = t * t); else t = clamp(x * scale, -sqrt2, sqrt2), u = t * t - 1
-template <int N, int K, bool RAW> __device__ __forceinline__ void gelu_pk_impl(f32x2 (&x)[N], const float (&c)[K], const float scale) {
+template <int N> __device__ __forceinline__ void gelu_pk_poly(f32x2 (&x)[N]) {
+    constexpr float c[11] = MLPK_GELUP_COEFS;
+    constexpr float scale = MLPK_GELUP_SCALE;
     constexpr float r2 = 1.41421356237f;
     f32x2 t[N], u[N], q[N];
-    if constexpr (RAW) {
 #pragma unroll
-        for (int k = 0; k < N; ++k) t[k] = f32x2{__builtin_amdgcn_fmed3f(x[k].x, -scale, scale), __builtin_amdgcn_fmed3f(x[k].y, -scale, scale)};
+    for (int k = 0; k < N; ++k) t[k] = x[k] * f32x2{scale, scale};
 #pragma unroll
-        for (int k = 0; k < N; ++k) u[k] = t[k] * t[k];
-    } else {
+    for (int k = 0; k < N; ++k) t[k] = f32x2{__builtin_amdgcn_fmed3f(t[k].x, -r2, r2), __builtin_amdgcn_fmed3f(t[k].y, -r2, r2)};
 #pragma unroll
-        for (int k = 0; k < N; ++k) t[k] = x[k] * f32x2{scale, scale};
-#pragma unroll
-        for (int k = 0; k < N; ++k) t[k] = f32x2{__builtin_amdgcn_fmed3f(t[k].x, -r2, r2), __builtin_amdgcn_fmed3f(t[k].y, -r2, r2)};
-#pragma unroll
-        for (int k = 0; k < N; ++k) u[k] = __builtin_elementwise_fma(t[k], t[k], f32x2{-1.0f, -1.0f});
-    }
+    for (int k = 0; k < N; ++k) u[k] = __builtin_elementwise_fma(t[k], t[k], f32x2{-1.0f, -1.0f});
 #pragma unroll
     for (int k = 0; k < N; ++k) q[k] = __builtin_elementwise_fma(u[k], f32x2{c[0], c[0]}, f32x2{c[1], c[1]});
 #pragma unroll
-    for (int i = 2; i < K; ++i)
+    for (int i = 2; i < 11; ++i)
 #pragma unroll
         for (int k = 0; k < N; ++k) q[k] = __builtin_elementwise_fma(q[k], u[k], f32x2{c[i], c[i]});
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] = x[k] * __builtin_elementwise_fma(t[k], q[k], f32x2{0.5f, 0.5f});
 }
 
+// gelu of N pairs for a 16-bit storage type T: bf16 -> h2b, f16 -> the centred polynomial
 template <typename T, int N> __device__ __forceinline__ void gelu_pk_n(f32x2 (&x)[N]) {
-#if !defined(MLPK_GELU_BF16_POLY) && !defined(MLPK_GELU_BF16_SIG)
     if constexpr (dtype_of<T>::value == MLPK_BF16) {
         if constexpr (N >= 2) {
             unsigned h[N];
@@ -195,38 +159,8 @@ template <typename T, int N> __device__ __forceinline__ void gelu_pk_n(f32x2 (&x
             const h2_t p = gelu_h2_phi(h2_t{(_Float16)x[0].x, (_Float16)x[0].y});
             x[0] = f32x2{x[0].x * (float)p.x, x[0].y * (float)p.y};
         }
-        return;
-    }
-#endif
-#ifndef MLPK_GELU_BF16_POLY
-    if constexpr (dtype_of<T>::value == MLPK_BF16) {
-        // the N pairs step by step (the compiler is free to pair the fma / mul steps into v_pk_*: same bits either way)
-        f32x2 a[N], q[N];
-#pragma unroll
-        for (int k = 0; k < N; ++k) a[k] = f32x2{__builtin_fabsf(x[k].x), __builtin_fabsf(x[k].y)};
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = __builtin_elementwise_fma(a[k], f32x2{MLPK_GELUS_K2, MLPK_GELUS_K2}, f32x2{MLPK_GELUS_K1, MLPK_GELUS_K1});
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = __builtin_elementwise_fma(a[k], q[k], f32x2{MLPK_GELUS_K0, MLPK_GELUS_K0});
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = x[k] * q[k];
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = f32x2{__builtin_amdgcn_exp2f(q[k].x), __builtin_amdgcn_exp2f(q[k].y)};
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = q[k] + f32x2{1.0f, 1.0f};
-#pragma unroll
-        for (int k = 0; k < N; ++k) q[k] = f32x2{__builtin_amdgcn_rcpf(q[k].x), __builtin_amdgcn_rcpf(q[k].y)};
-#pragma unroll
-        for (int k = 0; k < N; ++k) x[k] = x[k] * q[k];
-        return;
-    }
-#endif
-    if constexpr (dtype_of<T>::value == MLPK_BF16) {
-        constexpr float c[8] = MLPK_GELUP_COEFS_BF16;
-        gelu_pk_impl<N, 8, true>(x, c, MLPK_GELUP_CLAMP_BF16);
     } else {
-        constexpr float c[11] = MLPK_GELUP_COEFS;
-        gelu_pk_impl<N, 11, false>(x, c, MLPK_GELUP_SCALE);
+        gelu_pk_poly<N>(x);
     }
 }
 
@@ -237,29 +171,18 @@ template <typename T> __device__ __forceinline__ f32x2 gelu_pk(f32x2 x) {
 }
 
 // scalar form of gelu_pk (the same operation sequence, hence the same results)
-template <int K, bool RAW> __device__ __forceinline__ float gelu16_impl(float x, const float (&c)[K], const float scale) {
-    constexpr float r2 = 1.41421356237f;
-    const float t = RAW ? __builtin_amdgcn_fmed3f(x, -scale, scale) : __builtin_amdgcn_fmed3f(x * scale, -r2, r2);
-    const float u = RAW ? t * t : __builtin_fmaf(t, t, -1.0f);
-    float q = __builtin_fmaf(u, c[0], c[1]);
-#pragma unroll
-    for (int i = 2; i < K; ++i) q = __builtin_fmaf(q, u, c[i]);
-    return x * __builtin_fmaf(t, q, 0.5f);
-}
-
 template <typename T> __device__ __forceinline__ float gelu16_f(float x) {
-#if !defined(MLPK_GELU_BF16_POLY) && !defined(MLPK_GELU_BF16_SIG)
-    if constexpr (dtype_of<T>::value == MLPK_BF16) return gelu_h2b_f(x);
-#endif
-#ifndef MLPK_GELU_BF16_POLY
-    if constexpr (dtype_of<T>::value == MLPK_BF16) return gelu_sig_f(x);
-#endif
     if constexpr (dtype_of<T>::value == MLPK_BF16) {
-        constexpr float c[8] = MLPK_GELUP_COEFS_BF16;
-        return gelu16_impl<8, true>(x, c, MLPK_GELUP_CLAMP_BF16);
+        return gelu_h2b_f(x);
     } else {
         constexpr float c[11] = MLPK_GELUP_COEFS;
-        return gelu16_impl<11, false>(x, c, MLPK_GELUP_SCALE);
+        constexpr float r2 = 1.41421356237f;
+        const float t = __builtin_amdgcn_fmed3f(x * MLPK_GELUP_SCALE, -r2, r2);
+        const float u = __builtin_fmaf(t, t, -1.0f);
+        float q = __builtin_fmaf(u, c[0], c[1]);
+#pragma unroll
+        for (int i = 2; i < 11; ++i) q = __builtin_fmaf(q, u, c[i]);
+        return x * __builtin_fmaf(t, q, 0.5f);
     }
 }
 

@@ -359,7 +359,7 @@ extern "C" int mlpk_dwconv_affine_nhwc(int dtype, const void* x, void* out, int 
 // The taps are rounded to the activation dtype (they are MFMA operands); products and sums are fp32.
 //   * workgroup = 8 waves x 4 channels x a range of images.  32 channels = 64 contiguous, 64-byte-ALIGNED bytes of every
 //     channel-last pixel: at 24 channels (48-byte pieces, what the register file holds at k = 9) the same data movement alone
-//     took 1.12 ms per ConvMixer-1536/20 layer against 0.40 ms at 32 (tools/gpu_dwconv_variants.sh, profiles/r04_dwconv_*):
+//     took 1.12 ms per ConvMixer-1536/20 layer against 0.40 ms at 32 (profiles/r04_dwconv_*):
 //     pieces that end inside a 64-byte sector reach HBM as partial writes;
 //   * a wave keeps the k tap fragments of CREG of its channels in registers for the whole range; those of the other 4 - CREG
 //     live in the LDS as a table of the 16 distinct lane patterns (+ one of zeros) per (channel, tap row) -- a fragment only
@@ -377,24 +377,9 @@ extern "C" int mlpk_dwconv_affine_nhwc(int dtype, const void* x, void* out, int 
 //     on different banks in these 4-byte transposing accesses;
 //   * workgroups are dealt round-robin to the 8 XCDs, each with its own L2: the 8 workgroups of 8 NEIGHBOURING channel groups
 //     (4 whole 128-byte lines) go to ONE XCD at the same time, whose L2 then fetches a line once and writes whole lines back.
-#ifndef DWM_LOADS
-#define DWM_LOADS 3                                                 // experiment knobs of tools/gpu_dwconv_variants.sh
-#endif
-#ifndef DWM_CREG9
-#define DWM_CREG9 2
-#endif
-#ifndef DWM_CREG7
-#define DWM_CREG7 3
-#endif
-#ifndef DWM_XCD
-#define DWM_XCD 1
-#endif
-#ifndef DWM_STAGES
-#define DWM_STAGES 2
-#endif
-#ifndef DWM_SKIP
-#define DWM_SKIP 0                                                  // 1: no MFMA phase; 2: no global loads / stores; 4: no LDS transposes
-#endif
+constexpr int DWM_CREG9 = 2;                                        // channels of a wave whose tap fragments stay in registers, k = 9
+constexpr int DWM_CREG7 = 3;                                        // ... k = 7
+constexpr int DWM_STAGES = 2;                                       // plane-row fragment pairs in flight (profiles/r04_dwconv_variants.txt)
 constexpr int DWM_PITCH = 80;
 constexpr int DWM_PLANE = 40 * DWM_PITCH;
 constexpr int DWM_NPAT = 17;                                        // lane patterns of a tap fragment: 16 + all zeros
@@ -451,7 +436,6 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
     static_assert(CG % 8 == 0 && (512 * CH8) % NT == 0 && CREG >= 1 && CREG <= CPW, "workgroup geometry");
     static_assert(KS * KS * CG * 4 <= PLANES_END, "tap staging fits the planes");
     int gx = blockIdx.x, gy = blockIdx.y;
-#if DWM_XCD
     if (gridDim.x % 8 == 0 && (gridDim.x * gridDim.y) % 64 == 0) {     // (else the plain order: the deal below needs whole rounds)
         const int id = blockIdx.x + gridDim.x * blockIdx.y;
         const int xcd = id & 7, l = id >> 3;                        // l: this XCD's l-th workgroup
@@ -459,7 +443,6 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
         gx = (oct % octs) * 8 + (l & 7);
         gy = oct / octs;
     }
-#endif
     const int c0 = gx * CG;
     const int b0 = gy * img_per_wg;
     const int b1 = b0 + img_per_wg < B ? b0 + img_per_wg : B;
@@ -594,18 +577,13 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
     __syncthreads();                                                // planes zeroed
     lds_put();
     for (int b = b0; b < b1; ++b) {
-#if DWM_LOADS != 3
-        if (!(DWM_SKIP & 2) && b + 1 < b1) gload(b + 1);
-#endif
         __syncthreads();                                            // image b is in the planes
 #pragma unroll
-        for (int j = 0; j < ((DWM_SKIP & 1) ? 0 : CPW); ++j) {
-#if DWM_LOADS == 3
+        for (int j = 0; j < CPW; ++j) {
             if (b + 1 < b1) {
 #pragma unroll
                 for (int q = j * NSLOT / CPW; q < (j + 1) * NSLOT / CPW; ++q) gload_slot(b + 1, q);
             }
-#endif
             char* const plane = smem + dwm_plane_off(wave * CPW + j);
             const unsigned ab = (unsigned)(uintptr_t)((kq < 3 ? plane : zplane) + a_rd);
             const unsigned alo = ab + h0, ahi = ab + 8 - h0;
@@ -689,7 +667,7 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
         __syncthreads();                                            // results of image b are in the planes
         // ---- results out (two 16-byte stores per slot), next image in (same dwords) ----
 #pragma unroll
-        for (int q = 0; q < ((DWM_SKIP & 4) ? 0 : NSLOT); ++q) {
+        for (int q = 0; q < NSLOT; ++q) {
             int cq, yy, xx;
             slot_of(q, cq, yy, xx);
             if (!FULL && !(c0 + 8 * cq < C && yy < H && xx < W)) continue;
@@ -703,15 +681,10 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
             o0.z = __builtin_amdgcn_perm(d[5], d[4], 0x05040100); o1.z = __builtin_amdgcn_perm(d[5], d[4], 0x07060302);
             o0.w = __builtin_amdgcn_perm(d[7], d[6], 0x05040100); o1.w = __builtin_amdgcn_perm(d[7], d[6], 0x07060302);
             T* dstg = out + (((size_t)b * H + yy) * W + xx) * C + c0 + 8 * cq;
-#if DWM_SKIP & 2
-            if (o0.x == 0x12345678u && b == -1)
-#endif
-            {
-                *reinterpret_cast<u32x4*>(dstg) = o0;
-                if (FULL || xx + 1 < W) *reinterpret_cast<u32x4*>(dstg + C) = o1;
-            }
+            *reinterpret_cast<u32x4*>(dstg) = o0;
+            if (FULL || xx + 1 < W) *reinterpret_cast<u32x4*>(dstg + C) = o1;
         }
-        if (!(DWM_SKIP & 4) && b + 1 < b1) lds_put();
+        if (b + 1 < b1) lds_put();
     }
 }
 

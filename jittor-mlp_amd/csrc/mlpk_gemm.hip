@@ -45,8 +45,11 @@ struct GemmArgs {
     int vec_c, vec_r;   // vector (4-element) store / residual-load allowed
     // p8 launch (see gemm_nt_p8_kernel): row panels [m_base, m_base + panels * tile height), column groups
     int m_base, panels, cgroups;
-    void* prof_buf;     // MLPK_P8_PROF builds: per-workgroup cycle sums (reserved & 8)
-    int dbg;            // tuning bits (desc.reserved & 0xff, mlpk.h)
+    void* unused;       // eight bytes that keep the offsets of the fields behind them: without the slot hipcc's scalar-register allocation of the
+                        // persistent pair kernels changes (20 bytes of scratch where there were none, 76 where there were 60).  Like the store
+                        // condition in p8_store_tile it can go once that tile is re-measured without it: the figures that decided both are in the
+                        // message of the commit that removed the measurement paths ("After ABI 14")
+    int dbg;            // plan bits (desc.reserved & 0xf0, mlpk.h)
     // by-product row statistics of the stored values (16-bit row-major outputs): pair (q, m) = (sum, sum of squares) of row m over
     // column block q; block width 128 (LDS-staged epilogue) or 32 (direct epilogue of the persistent tile).  PLANAR, one plane per
     // column block: a tile's pairs are one contiguous run (256 rows x 8 bytes), written as whole cache lines -- interleaved per
@@ -60,11 +63,6 @@ struct GemmArgs {
 };
 
 __device__ __attribute__((aligned(64))) unsigned g_zero_slab[16];      // 64 zero bytes: the slab of a tap outside the map
-
-// tuning aid (dbg & 8): wave 0 / lane 0 of each workgroup logs s_memtime stamps into the buffer passed in R
-#define MLPK_STAMP(slot)                                                                          \
-    if ((p.dbg & 8) && threadIdx.x == 0 && (slot) < 64)                                            \
-        reinterpret_cast<unsigned long long*>(const_cast<void*>(p.R))[(size_t)blockIdx.x * 64 + (slot)] = __builtin_readcyclecounter();
 
 // One 1-KiB LDS-DMA piece: 64 lanes x 16 bytes, per-lane global source, LDS destination = M0 base + lane*16.
 // Inline asm on purpose: hipcc tracks the builtin form as an LDS store and drains vmcnt(0) in front of any
@@ -185,15 +183,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
         if constexpr (SPLIT) return (j / (FN / 2)) * (BN / 2) + wn * (TN / 2) + (j % (FN / 2)) * 16;
         else return wn * TN + j * 16;
     };
-    if (p.dbg & 4) {
-        float sacc = 0.f;
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-            for (int j = 0; j < FN; ++j) sacc += acc[i][j].x + acc[i][j].y + acc[i][j].z + acc[i][j].w;
-        if (sacc == 123.456f) reinterpret_cast<float*>(p.C)[0] = sacc;
-        return;
-    }
     T* __restrict__ C = reinterpret_cast<T*>(p.C);
     const T* R = reinterpret_cast<const T*>(p.R);
     const bool gelu = p.act == MLPK_ACT_GELU;
@@ -326,7 +315,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
                     }
                     __builtin_memcpy(&outv, a8, 16);
                 }
-                if (gm < p.M && live && (!(p.dbg & 2) || outv.x == 0x12345678u))
+                if (gm < p.M && live)
                     *reinterpret_cast<u32x4*>(C + (size_t)gm * p.ldc + gn) = outv;
                 if constexpr (STATS && CPR >= 16) {
                     ps1[q] = 0.f; ps2[q] = 0.f;
@@ -409,7 +398,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = (p.res_mode == MLPK_RES_ADD) ? v[r] + rv[r] : v[r] * rv[r];
                     }
-                    if (!(p.dbg & 2) || v[0] == 123.456f) store4<T>(C + co, p.vec_c != 0, v);
+                    store4<T>(C + co, p.vec_c != 0, v);
                 } else {
                     for (int r = 0; r < 4 && nb + r < p.N; ++r) {
                         float t = v[r];
@@ -430,7 +419,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x4 (&acc)[BM
             // traffic (store, and the residual / gate operand) is 16 bytes per lane in whole BM-channel runs per token;
             // the accumulator layout itself only gives 8-byte pieces in 32-byte runs.
             const bool has_res = p.res_mode != MLPK_RES_NONE;
-            if (p.t_rows % BM == 0 && m0 + BM <= p.M && p.vec_c == 2 && (!has_res || p.vec_r == 2) && !(p.dbg & 2)) {
+            if (p.t_rows % BM == 0 && m0 + BM <= p.M && p.vec_c == 2 && (!has_res || p.vec_r == 2)) {
                 constexpr int CPT = BM / 8;                      // 16-byte chunks per token row
                 constexpr int XT = (CPT >= 16 ? 16 : CPT) - 1;
                 constexpr int TPP = NT / CPT;                    // tokens moved per pass
@@ -566,7 +555,7 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_nt_kernel(const GemmArgs p) 
     u32x4 ra[A_IT], rb[B_IT];
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
-    const int nk = (p.dbg & 1) ? 0 : (p.K + BK - 1) / BK;
+    const int nk = (p.K + BK - 1) / BK;
 
 #define MLPK_GLOAD(kt)                                                                           \
     {                                                                                            \
@@ -671,25 +660,17 @@ __global__ void __launch_bounds__(WM* WN * 64) gemm_nt_kernel(const GemmArgs p) 
         _Pragma("unroll") for (int g = 0; g < B_G; ++g)                                          \
             __builtin_amdgcn_global_load_lds((glb_ptr_t)(srcB[g] + k__), (lds_ptr_t)(dstb__ + g * 1024), 16, 0, 0); \
     }
-        MLPK_STAMP(0);
         MLPK_STAGE(0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        MLPK_STAMP(1);
         for (int kt = 0; kt < nk; ++kt) {
             if ((kt + 1) < nk) MLPK_STAGE(kt + 1);
-            MLPK_STAMP(2 + 4 * kt);
             MLPK_COMPUTE(kt);
-            MLPK_STAMP(3 + 4 * kt);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            MLPK_STAMP(4 + 4 * kt);
             __syncthreads();
-            MLPK_STAMP(5 + 4 * kt);
         }
 #undef MLPK_STAGE
     }
-    MLPK_STAMP(60);
-    if (p.dbg & 8) return;
 #undef MLPK_COMPUTE
 #undef MLPK_GLOAD
 #undef MLPK_SSTORE
@@ -768,7 +749,7 @@ __device__ __forceinline__ void gemm_nt_s3_body(const GemmArgs& p, const int bid
     };
     typedef __attribute__((address_space(3))) void* lds_ptr_t;
     typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-    const int nk = (p.dbg & 1) ? 0 : p.K / BK;
+    const int nk = p.K / BK;
 
     const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)smem;
     const unsigned dst_a = __builtin_amdgcn_readfirstlane(lds_base + wave * (A_G * 1024));
@@ -795,20 +776,15 @@ __device__ __forceinline__ void gemm_nt_s3_body(const GemmArgs& p, const int bid
     const int co = (fg ^ ((frow & 8) >> 2)) << 4;
     const int a_rd = (wm * TM + frow) * 64 + co;
     const int b_rd = BM * 64 + (wn * TN + frow) * 64 + co;
-
-    MLPK_STAMP(0);
     if (nk > 0) S3_STAGE(0);
     if (nk > 1) S3_STAGE(1);
-    MLPK_STAMP(1);
     for (int kt = 0; kt < nk; ++kt) {
-        MLPK_STAMP(2 + 2 * kt);
         // own pieces of slab kt have landed (slab kt+1, if issued, may still be in flight) ...
         if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // ... and after the barrier everybody's have; every wave is also past its reads of slab kt-1,
         // whose stage is the one refilled next.
         __builtin_amdgcn_s_barrier();
-        MLPK_STAMP(3 + 2 * kt);
         const char* buf = smem + (kt % 3) * STAGE_B;
         u32x4 af[FM], bf[FN];
 #pragma unroll
@@ -834,10 +810,7 @@ __device__ __forceinline__ void gemm_nt_s3_body(const GemmArgs& p, const int bid
     }
 #undef S3_PIECE
 #undef S3_STAGE
-    MLPK_STAMP(60);
     __syncthreads();
-    MLPK_STAMP(61);
-    if (p.dbg & 8) return;
     gemm_epilogue<T, BM, BN, WM, WN, TRANS>(p, acc, smem, m0, n0, threadIdx.x);
 }
 
@@ -930,19 +903,7 @@ __device__ __forceinline__ void glds_piece_s(unsigned voff, const void* sbase, u
 // vectors up front, the element math is branch-free and written on float pairs (v_pk_* issue).
 template <typename T, bool GELU, bool LN, bool AFF>
 __device__ __forceinline__ void p8_store_tile(const GemmArgs& p, f32x4 (&acc)[8][4], char* stg, const int m0, const int n0,
-                                              const int tid, unsigned long long (&prof)[8]) {
-#ifdef MLPK_P8_PROF   // fine-grained epilogue stamps cost registers: tuning builds only (-DMLPK_P8_PROF)
-    const bool stamp = (p.dbg & 8) != 0;
-    unsigned long long tprev = stamp ? __builtin_readcyclecounter() : 0;
-#define P8_PROF(k)                                                           \
-    if (stamp) {                                                             \
-        const unsigned long long n__ = __builtin_readcyclecounter();          \
-        prof[k] += n__ - tprev;                                               \
-        tprev = n__;                                                          \
-    }
-#else
-#define P8_PROF(k)
-#endif
+                                              const int tid) {
     const int lane = tid & 63;
     const int wave = tid >> 6;
     const int grp = wave >> 2, wn = wave & 3;
@@ -1026,9 +987,7 @@ __device__ __forceinline__ void p8_store_tile(const GemmArgs& p, f32x4 (&acc)[8]
                 }
             }
         }
-        P8_PROF(hm * 4 + 0);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        P8_PROF(hm * 4 + 1);
         // phase 2: 16-byte chunks LDS -> (residual) -> global, whole 512-byte rows per 32 lanes
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -1046,17 +1005,19 @@ __device__ __forceinline__ void p8_store_tile(const GemmArgs& p, f32x4 (&acc)[8]
                 }
                 __builtin_memcpy(&outv, a8, 16);
             }
+            // This condition is always true: gemm_prepare masks bit 2 of `dbg` away (it once meant "no stores" in timing runs), so no caller can
+            // make it false.  It stays, here and in p8_store_direct, because hipcc schedules both epilogues differently around plain stores --
+            // 10 to 13 more registers in the short-tile kernels, 20 to 28 more bytes of scratch in the 256-row ones -- and the models whose
+            // GEMMs take this tile measured 1 .. 5 % slower on one box in alternation (Mixer-S/16, ResMLP-24, AS-MLP-T, MS-MLP-T, Swin-MLP-T).
+            // The register-staged and s3 tiles store plainly.  (Per-model figures: the message of the commit that removed the measurement paths.)
             if (!(p.dbg & 2) || outv.x == 0x12345678u) {
                 u32x4* dst = reinterpret_cast<u32x4*>(C + (size_t)(m0 + hm * 128 + row) * p.ldc + gn);
                 if (p.dbg & 32) __builtin_nontemporal_store(outv, dst);
                 else *dst = outv;
             }
         }
-        P8_PROF(hm * 4 + 2);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        P8_PROF(hm * 4 + 3);
     }
-#undef P8_PROF
 }
 
 // Direct epilogue of the p8 kernel (2-byte row-major outputs, whole tiles): NO LDS round trip and NO barrier.
@@ -1078,14 +1039,6 @@ __device__ __forceinline__ void p8_store_tile(const GemmArgs& p, f32x4 (&acc)[8]
 // CUs' store bursts: the folded LayerNorm cost fc1 22 us = 8 %, almost all of it waiting); issued in the second-to-last K
 // slab the same wait merely moved into the last slab's vmcnt(0).  (Registers instead of LDS do not fit: 192 live + 48.)
 // LDS image: [0, 1 KiB) ln_mean of logical tile rows 0..255, [1, 2) ln_rstd, [2, 3) bias of tile columns 0..255, [3, 4) ln_csum.
-// 0: the statistics epilogue loads its residual chunks by untracked asm and waits for each by count (round 6 experiment: the
-// compiler's own waits cannot count the stores issued since, so from the fifth chunk on every step waits for the stores of four steps
-// earlier to be acknowledged).  Measured NEUTRAL on one box in alternation (profiles/r06_p8_counted_epilogue_ab.txt: Mixer-B/16 7.331 /
-// 7.298 / 7.335 ms against 7.333 / 7.311 / 7.327; ResMLP-24, gMLP-S within 0.2 %): the 20 k cycles of a tile's epilogue are its ~1800
-// VALU instructions per wave, not the write latency.  The tracked form stays the default (nothing to keep in step with the compiler).
-#ifndef P8_RES_TRACKED
-#define P8_RES_TRACKED 1
-#endif
 #define P8_PAR_OFF (2 * 4 * 128 * 128)
 #define P8_LDS_BYTES (P8_PAR_OFF + 2 * 4096)
 
@@ -1126,60 +1079,6 @@ __device__ __forceinline__ void p8_par_prefetch(const GemmArgs& p, const int m0,
     }
 }
 
-// s_waitcnt vmcnt(n) for an n that is a constant once the epilogue's loops are unrolled
-__device__ __forceinline__ void p8_wait_vm(const int n) {
-    switch (n) {
-        case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-        case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-        case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-        case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-        case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-        case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-        case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-        case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-        case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-        case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-        case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-        case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-        case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-        case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-        case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-        case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-        case 23: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-        case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-        case 25: asm volatile("s_waitcnt vmcnt(25)" ::: "memory"); break;
-        case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-        case 27: asm volatile("s_waitcnt vmcnt(27)" ::: "memory"); break;
-        case 28: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
-        case 29: asm volatile("s_waitcnt vmcnt(29)" ::: "memory"); break;
-        case 30: asm volatile("s_waitcnt vmcnt(30)" ::: "memory"); break;
-        case 31: asm volatile("s_waitcnt vmcnt(31)" ::: "memory"); break;
-        case 32: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-        case 33: asm volatile("s_waitcnt vmcnt(33)" ::: "memory"); break;
-        case 34: asm volatile("s_waitcnt vmcnt(34)" ::: "memory"); break;
-        case 35: asm volatile("s_waitcnt vmcnt(35)" ::: "memory"); break;
-        case 36: asm volatile("s_waitcnt vmcnt(36)" ::: "memory"); break;
-        case 37: asm volatile("s_waitcnt vmcnt(37)" ::: "memory"); break;
-        case 38: asm volatile("s_waitcnt vmcnt(38)" ::: "memory"); break;
-        case 39: asm volatile("s_waitcnt vmcnt(39)" ::: "memory"); break;
-        case 40: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-        case 41: asm volatile("s_waitcnt vmcnt(41)" ::: "memory"); break;
-        case 42: asm volatile("s_waitcnt vmcnt(42)" ::: "memory"); break;
-        case 43: asm volatile("s_waitcnt vmcnt(43)" ::: "memory"); break;
-        case 44: asm volatile("s_waitcnt vmcnt(44)" ::: "memory"); break;
-        case 45: asm volatile("s_waitcnt vmcnt(45)" ::: "memory"); break;
-        case 46: asm volatile("s_waitcnt vmcnt(46)" ::: "memory"); break;
-        case 47: asm volatile("s_waitcnt vmcnt(47)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
 template <typename T, bool GELU, bool LN, bool AFF, bool RES, int NI, bool STATS = false>
 __device__ __forceinline__ void p8_store_direct(const GemmArgs& p, f32x4 (&acc)[2 * NI][4], const char* par_lds, const int m0, const int n0,
                                                 const int tid) {
@@ -1208,12 +1107,11 @@ __device__ __forceinline__ void p8_store_direct(const GemmArgs& p, f32x4 (&acc)[
     // residual chunks of BOTH halves in flight before any math: the load latency (and the burst of every CU reading its
     // residual tile at once) is paid once per tile, the second half arrives under the first half's math
     u32x4 rr[RES ? 2 : 1][RES ? NI : 1][2];
-    // COUNTED (round 6, the statistics epilogue = the residual-stream GEMMs): the residual chunks are loaded by asm the compiler does not
-    // track and each is waited for by count.  Tracked, the compiler's wait in front of chunk s counted the 15 - s chunks behind it but
-    // not the stores issued since (it cannot tell how many of them ran: they sit in conditional blocks) -- so from the fifth chunk on
-    // every step waited for the STORES of four steps earlier to be acknowledged, and the last one for all of them: an epilogue paced by
-    // the write latency (11 us per 256-row tile where its instructions take 5).  P8_RES_TRACKED=1 rebuilds the old form for A/B.
-    constexpr bool COUNTED = RES && STATS && !P8_RES_TRACKED;
+    // The chunks are ordinary loads the compiler tracks: its wait in front of chunk s counts the 15 - s chunks behind it but not the
+    // stores issued since (they sit in conditional blocks), so from the fifth chunk on a step also waits for the stores of four steps
+    // earlier.  Loading them by untracked asm and waiting for each by count (round 6) was measured neutral and not kept
+    // (profiles/r06_p8_counted_epilogue_ab.txt: the 20 k cycles of a tile's epilogue are its ~1800 VALU instructions per wave, not the
+    // write latency).
     if constexpr (has_res) {
 #pragma unroll
         for (int hm = 0; hm < 2; ++hm)
@@ -1222,11 +1120,8 @@ __device__ __forceinline__ void p8_store_direct(const GemmArgs& p, f32x4 (&acc)[
 #pragma unroll
                 for (int hn = 0; hn < 2; ++hn) {
                     const T* src = R + (size_t)(m0 + hm * (NI * 32) + grp * (NI * 16) + i4 * 16 + frow) * p.ldr + n0 + hn * 128 + wn * 32 + ccol;
-                    if constexpr (COUNTED) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rr[hm][i4][hn]) : "v"(src) : "memory");
-                    else rr[hm][i4][hn] = *reinterpret_cast<const u32x4*>(src);
+                    rr[hm][i4][hn] = *reinterpret_cast<const u32x4*>(src);
                 }
-        // (tuning mode "no stores": the counts below assume the stores of the steps before)
-        if (COUNTED && (p.dbg & 2)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     float lmu[2][NI], lrs[2][NI];
     if (LN) {
@@ -1281,14 +1176,6 @@ __device__ __forceinline__ void p8_store_direct(const GemmArgs& p, f32x4 (&acc)[
                 const auto s0 = __builtin_amdgcn_permlane16_swap(w[0], w[2], false, false);
                 const auto s1 = __builtin_amdgcn_permlane16_swap(w[1], w[3], false, false);
                 u32x4 outv = {s0[0], s1[0], s0[1], s1[1]};
-                if constexpr (COUNTED) {
-                    // chunk `step` has landed when at most the chunks behind it and the two stores (row, statistics pair) of every step
-                    // before are still in flight; the empty statement hands the registers to the compiler only here
-                    constexpr int NCH = 4 * NI;
-                    const int step = (hm * NI + i4) * 2 + hn;
-                    p8_wait_vm(NCH - 1 - step + 2 * step);
-                    asm volatile("" : "+v"(rr[hm][i4][hn]));
-                }
                 if constexpr (has_res) {
                     T a8[8], r8[8];
                     __builtin_memcpy(a8, &outv, 16);
@@ -1300,7 +1187,7 @@ __device__ __forceinline__ void p8_store_direct(const GemmArgs& p, f32x4 (&acc)[
                     }
                     __builtin_memcpy(&outv, a8, 16);
                 }
-                if (!(p.dbg & 2) || outv.x == 0x12345678u)
+                if (!(p.dbg & 2) || outv.x == 0x12345678u)        // (always true, kept for the schedule it gives: see p8_store_tile)
                     *reinterpret_cast<u32x4*>(C + grow * p.ldc + n0 + hn * 128 + wn * 32 + ccol) = outv;
                 if constexpr (STATS) {
                     // by-product statistics of the stored values: this wave's 32 columns of row `grow` sit in the four lanes
@@ -1433,22 +1320,6 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
 
     const int nk = __builtin_amdgcn_readfirstlane(p.K / BK);   // >= 2 (host checked)
 
-#ifdef MLPK_P8_PROF   // tuning builds only (tools/gemm_p8_timeline.py): per-workgroup sums of [first slabs | main loop | epilogue]
-    unsigned long long tw = 0, tl = 0, te = 0, ts = 0;
-    unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int ntiles = 0;
-    const unsigned long long wall0 = wall_clock64(), cyc0 = __builtin_readcyclecounter();   // 100 MHz constant clock: start / end skew between CUs
-#define P8_STAMP(acc_)                                                       \
-    {                                                                        \
-        const unsigned long long n__ = __builtin_readcyclecounter();          \
-        acc_ += n__ - ts;                                                     \
-        ts = n__;                                                             \
-    }
-#else
-    unsigned long long prof[8];
-#define P8_STAMP(acc_)
-#endif
-
     // ---- first tile: slab 0 complete before the loop, three half-tiles of slab 1 in flight ----
     setup(l);
     int par_sel = 0;                                        // parameter buffer of the CURRENT tile
@@ -1457,13 +1328,9 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
     stage(1, 2); stage(1, 0); stage(1, 3);
 
     for (;;) {
-#ifdef MLPK_P8_PROF
-        ts = __builtin_readcyclecounter();
-#endif
         asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         P8_BARRIER();
         if (grp == 1) P8_BARRIER();
-        P8_STAMP(tw);
 
         // fragment read offsets, recomputed per tile from an opaque copy of the lane id: as launch-wide constants they
         // would be live across the register-hungry epilogue, and hipcc then spills them and reloads them INSIDE the K loop
@@ -1538,7 +1405,6 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         if (grp == 0) P8_BARRIER();
         // every wave is past all its LDS reads of this tile; the groups are aligned again
-        P8_STAMP(tl);
 
         const int cm0 = m0, cn0 = n0;
         l += lstep;
@@ -1580,14 +1446,14 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
         } else {
             char* stg = smem + BUF_B;
             switch (cls) {
-                case 0: p8_store_tile<T, false, false, false>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 1: p8_store_tile<T, true, false, false>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 2: p8_store_tile<T, false, true, false>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 3: p8_store_tile<T, true, true, false>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 4: p8_store_tile<T, false, false, true>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 5: p8_store_tile<T, true, false, true>(p, acc, stg, cm0, cn0, etid, prof); break;
-                case 6: p8_store_tile<T, false, true, true>(p, acc, stg, cm0, cn0, etid, prof); break;
-                default: p8_store_tile<T, true, true, true>(p, acc, stg, cm0, cn0, etid, prof); break;
+                case 0: p8_store_tile<T, false, false, false>(p, acc, stg, cm0, cn0, etid); break;
+                case 1: p8_store_tile<T, true, false, false>(p, acc, stg, cm0, cn0, etid); break;
+                case 2: p8_store_tile<T, false, true, false>(p, acc, stg, cm0, cn0, etid); break;
+                case 3: p8_store_tile<T, true, true, false>(p, acc, stg, cm0, cn0, etid); break;
+                case 4: p8_store_tile<T, false, false, true>(p, acc, stg, cm0, cn0, etid); break;
+                case 5: p8_store_tile<T, true, false, true>(p, acc, stg, cm0, cn0, etid); break;
+                case 6: p8_store_tile<T, false, true, true>(p, acc, stg, cm0, cn0, etid); break;
+                default: p8_store_tile<T, true, true, true>(p, acc, stg, cm0, cn0, etid); break;
             }
         }
         // A wait hipcc can SEE (the asm ones are opaque to it): every load of the epilogue has landed.  Without it the
@@ -1595,27 +1461,12 @@ __device__ __forceinline__ void p8_body(const GemmArgs& p, char* const smem) {
         // protects the first fragment reads of every slab with s_waitcnt vmcnt(0..4) -- which drains the LDS-DMA prefetch
         // queue it knows nothing about (tools/isa_lint.py).  Here it costs nothing extra: the loop-top vmcnt(6) waits
         // for the same stores anyway, and only slab 1's pieces are issued behind it.
-        // (round 6: the statistics epilogue loads its residual by untracked asm and waits by count -- nothing for the compiler to carry,
-        // and slab 1's pieces leave straight behind the last store instead of after its acknowledgement)
-        if constexpr (!(EPI == 2 && !P8_RES_TRACKED)) __builtin_amdgcn_s_waitcnt(0x0F70);
+        // (Every epilogue loads its residual by tracked loads, the statistics one included: the counted, untracked form that needed no
+        // wait here was measured and not kept.)
+        __builtin_amdgcn_s_waitcnt(0x0F70);
         if (more) { stage(1, 2); stage(1, 0); stage(1, 3); }
-#ifdef MLPK_P8_PROF
-        P8_STAMP(te);
-        ++ntiles;
-#endif
         if (!more) break;
     }
-#ifdef MLPK_P8_PROF
-    if ((p.dbg & 8) && tid == 0) {
-        // (a pair launch runs two bodies: the second one, m_base != 0, reports 16 slots further on)
-        unsigned long long* o = reinterpret_cast<unsigned long long*>(p.prof_buf) + (size_t)blockIdx.x * 64 + (p.m_base ? 16 : 0);
-        o[0] = tw; o[1] = tl; o[2] = te; o[3] = (unsigned long long)ntiles;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[4 + k] = prof[k];
-        o[12] = wall0; o[13] = wall_clock64(); o[14] = __builtin_readcyclecounter() - cyc0;
-    }
-#endif
-#undef P8_STAMP
 }
 
 template <typename T, int EPI, int NI>
@@ -2053,8 +1904,8 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
     a.rperiod = d->rperiod > 0 ? d->rperiod : 1;
     a.act = d->act; a.res_mode = d->res_mode;
     a.t_rows = d->t_rows; a.t_tokens = d->t_tokens;
-    a.dbg = d->reserved & 0xff;
-    a.m_base = 0; a.panels = 0; a.cgroups = 1; a.prof_buf = d->workspace;
+    a.dbg = d->reserved & 0xf0;
+    a.m_base = 0; a.panels = 0; a.cgroups = 1; a.unused = nullptr;
     a.row_part = d->row_part; a.row_part_ld = d->row_part_ld;
     const int vb = 4 * es;   // bytes of a 4-element vector
     a.vec_c = (d->ldc % 4 == 0) && (((uintptr_t)d->C % vb) == 0);
@@ -2168,9 +2019,6 @@ extern "C" int mlpk_gemm_nt(const mlpk_gemm_desc* d, void* stream) {
     }
 }
 
-extern "C" int mlpk_conv_gemm_nhwc_supported(int dtype, int Cin, int kh, int kw, int stride, int pad);
-extern "C" int mlpk_conv_gemm_nhwc(const mlpk_gemm_desc* d, int B, int H, int W, int Cin, int kh, int kw, int stride, int pad, void* stream);
-
 // conv_src divides n < n_max by d with one multiply by m = ceil(2^16 / d) and a 16-bit shift: kt / cpk (n_max = kh kw cpk) and tap / kw
 // (n_max = kh kw).  With e = m d - 2^16 that is exact for every n < n_max iff (n_max - 1) e < 2^16 (n_max is a multiple of d, so n_max - 1
 // has the worst remainder, d - 1).  Shapes that fail it are refused rather than divided wrongly (7 x 7, Cin 1536: cpk 48, e 32, kt 2351 gave
@@ -2215,8 +2063,6 @@ extern "C" int mlpk_conv_gemm_nhwc(const mlpk_gemm_desc* d, int B, int H, int W,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     return d->dtype == MLPK_F16 ? launch_s3_conv<f16_t>(a, s) : launch_s3_conv<bf16_t>(a, s);
 }
-
-extern "C" int mlpk_gemm_nt_pair(const mlpk_gemm_desc* d0, const mlpk_gemm_desc* d1, void* stream);
 
 // two products in one launch where the dispatch gives both the same "s3" tile (row-major outputs, 16-bit); anything else: one after the other
 extern "C" int mlpk_gemm_nt_pair(const mlpk_gemm_desc* d0, const mlpk_gemm_desc* d1, void* stream) {

@@ -184,9 +184,6 @@ static int hire_geometry(int B, int H, int W, int C, int h, int w, int dtype, in
 
 using namespace mlpk;
 
-extern "C" int mlpk_hire_gather_ln(int dtype, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, void* a_h,
-                                   void* a_w, int B, int H, int W, int C, int h, int w, int step, int ld_h, int ld_w, void* stream);
-
 extern "C" int mlpk_hire_gather(int dtype, const void* xn, void* a_h, void* a_w, int B, int H, int W, int C, int h, int w,
                                 int step, int ld_h, int ld_w, void* stream) {
     return mlpk_hire_gather_ln(dtype, xn, nullptr, nullptr, nullptr, nullptr, a_h, a_w, B, H, W, C, h, w, step, ld_h, ld_w, stream);
@@ -216,9 +213,6 @@ extern "C" int mlpk_hire_gather_ln(int dtype, const void* xn, const float* mean,
     return 0;
 }
 
-extern "C" int mlpk_hire_combine_from(int dtype, void* x, const void* src, const void* y_h, const void* y_w, int B, int H, int W, int C, int h, int w,
-                                      int step, int ld_h, int ld_w, void* stream);
-
 extern "C" int mlpk_hire_combine(int dtype, void* x, const void* y_h, const void* y_w, int B, int H, int W, int C, int h, int w,
                                  int step, int ld_h, int ld_w, void* stream) {
     return mlpk_hire_combine_from(dtype, x, x, y_h, y_w, B, H, W, C, h, w, step, ld_h, ld_w, stream);
@@ -247,9 +241,6 @@ extern "C" int mlpk_hire_combine_from(int dtype, void* x, const void* src, const
     MLPK_LAUNCH_CHECK();
     return 0;
 }
-
-extern "C" int mlpk_hire_combine_stats(int dtype, void* x, const void* src, const void* y_h, const void* y_w, int B, int H, int W, int C, int h, int w,
-                                       int step, int ld_h, int ld_w, float* out_mean, float* out_rstd, float eps, void* stream);
 
 extern "C" int mlpk_hire_combine_stats(int dtype, void* x, const void* src, const void* y_h, const void* y_w, int B, int H, int W, int C, int h, int w,
                                        int step, int ld_h, int ld_w, float* out_mean, float* out_rstd, float eps, void* stream) {
@@ -982,16 +973,14 @@ template <> struct SwinMma<f16_t> {
     }
 };
 
-#ifndef SW_RELOAD
-#define SW_RELOAD 0                                          // (measured: 4.53 vs 4.43 ms on Swin-MLP-T -- fewer registers, more windows per CU, no gain)
-#endif
 constexpr int SW_NT = 256;
 constexpr int SW_TPITCH = 64 * 2 + 16;                       // LDS row of the transposed image: 64 tokens + 16 bytes (bank spread)
 constexpr int SW_MAXI = 20;                                  // (token, 8-channel chunk) items per thread: ws^2 * C / 8 / 256 <= 20 (C <= 768 at ws = 7)
 
 // MAXI = (token, chunk) items per thread, NHW = heads per wave: sized to the width (registers decide how many windows a CU holds at once)
-// (RELOAD: the raw values are read again for the residual -- cache hits -- instead of being held in registers across the products)
-template <typename T, int MAXI, int NHW, bool RELOAD>
+// (The raw values are held in registers across the products for the residual.  Reading them again instead -- cache hits, fewer registers,
+// more windows per CU -- was measured and not kept: 4.53 vs 4.43 ms on Swin-MLP-T.)
+template <typename T, int MAXI, int NHW>
 __global__ void __launch_bounds__(SW_NT) swin_spatial_kernel(const SwinArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_sw[];
     T* __restrict__ x = reinterpret_cast<T*>(p.x);
@@ -1007,12 +996,12 @@ __global__ void __launch_bounds__(SW_NT) swin_spatial_kernel(const SwinArgs p) {
         const int ch = i / (64 - T2), t = T2 + i % (64 - T2);
         *reinterpret_cast<T*>(smem_sw + ch * SW_TPITCH + t * 2) = from_f32<T>(0.f);
     }
-    u32x4 raw[RELOAD ? 1 : MAXI];
+    u32x4 raw[MAXI];
     const float inv_cv = 1.0f / (float)CV, inv_ws = 1.0f / (float)ws;
 #pragma unroll
     for (int k = 0; k < MAXI; ++k) {
         const int it = tid + k * SW_NT;
-        if (!RELOAD) raw[RELOAD ? 0 : k] = u32x4{0u, 0u, 0u, 0u};
+        raw[k] = u32x4{0u, 0u, 0u, 0u};
         if (it < nitem) {
             const int t = (int)(((float)it + 0.5f) * inv_cv), cq = it - t * CV;
             const int ty = (int)(((float)t + 0.5f) * inv_ws), tx = t - ty * ws;
@@ -1020,7 +1009,7 @@ __global__ void __launch_bounds__(SW_NT) swin_spatial_kernel(const SwinArgs p) {
             const bool inside = (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
             const size_t row = ((size_t)b * p.H + (inside ? yy : 0)) * p.W + (inside ? xx : 0);
             const u32x4 v = *reinterpret_cast<const u32x4*>(x + row * C + cq * 8);
-            if (!RELOAD) raw[RELOAD ? 0 : k] = v;
+            raw[k] = v;
             const float mu = p.mean[row], rs = p.rstd[row];
             T e[8];
             __builtin_memcpy(e, &v, 16);
@@ -1104,7 +1093,7 @@ __global__ void __launch_bounds__(SW_NT) swin_spatial_kernel(const SwinArgs p) {
             if ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W) {
                 const u32x4 yv = *reinterpret_cast<const u32x4*>(smem_sw + t * opitch + cq * 16);
                 T a[8], y8[8], o[8];
-                const u32x4 rv = RELOAD ? *reinterpret_cast<const u32x4*>(x + (((size_t)b * p.H + yy) * p.W + xx) * C + cq * 8) : raw[RELOAD ? 0 : k];
+                const u32x4 rv = raw[k];
                 __builtin_memcpy(a, &rv, 16);
                 __builtin_memcpy(y8, &yv, 16);
 #pragma unroll
@@ -1340,10 +1329,6 @@ extern "C" int mlpk_swin_spatial_supported(int dtype, int C, int heads, int ws) 
            (ws * ws * (C / 8) + SW_NT - 1) / SW_NT <= SW_MAXI;
 }
 
-extern "C" int mlpk_swin_spatial_stats(int dtype, void* x, int B, int H, int W, int C, int ws, int pad_t, int pad_l, int Hp, int Wp, int heads,
-                                       const float* mean, const float* rstd, const float* gamma, const float* beta, const void* w, const float* bias,
-                                       float* out_mean, float* out_rstd, float eps, void* stream);
-
 extern "C" int mlpk_swin_spatial(int dtype, void* x, int B, int H, int W, int C, int ws, int pad_t, int pad_l, int Hp, int Wp, int heads,
                                  const float* mean, const float* rstd, const float* gamma, const float* beta, const void* w, const float* bias,
                                  void* stream) {
@@ -1396,7 +1381,7 @@ extern "C" int mlpk_swin_spatial_stats(int dtype, void* x, int B, int H, int W, 
     }
 #define SW_LAUNCH(TT, MAXI, NHW)                                                                                           \
     do {                                                                                                                   \
-        auto k = swin_spatial_kernel<TT, MAXI, NHW, (MAXI > 3) && SW_RELOAD>;                                                                       \
+        auto k = swin_spatial_kernel<TT, MAXI, NHW>;                                                                       \
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);        \
         if (e != hipSuccess) return (int)e;                                                                                \
         hipLaunchKernelGGL(k, dim3((unsigned)nwin), dim3(SW_NT), lds, s, a);                                               \
@@ -1430,11 +1415,6 @@ static int mixshift_args(mlpk::MixShiftArgs& a, int dtype, const void* x, void* 
     }
     return 0;
 }
-
-extern "C" int mlpk_mixshift_stats_planes(int dtype, int B, int H, int W, int C, int groups, const int* ksize);
-extern "C" int mlpk_mixshift_nhwc_stats(int dtype, const void* x, void* out, int B, int H, int W, int C, int groups, const int* shift,
-                                        const int* ksize, const float* w_lr, const float* b_lr, const float* w_td, const float* b_td,
-                                        float* row_part, long long row_part_ld, void* stream);
 
 // planes of by-product statistics mlpk_mixshift_nhwc_stats writes for this shape (C / 32), 0 when it does not take the shape
 extern "C" int mlpk_mixshift_stats_planes(int dtype, int B, int H, int W, int C, int groups, const int* ksize) {

@@ -90,9 +90,6 @@ constexpr int TM_LDS = TM_B2 + 16 * (TM_NB0 + TM_NB1) * 4;
 
 // iteration flavours: RAMP (t < 2, run-time predicates), STEADY (branch-free), DRAIN (t >= G, t >= 2: no fc1 code at all,
 // which leaves the registers of its operands to the residual tile that is requested during the last iteration)
-#ifndef TM_ABL
-#define TM_ABL 0      // tuning aid (tools/build_variant.sh): 1 no in-loop LDS-DMA, 2 identity GELU, 4 no fc1 MFMAs, 8 no fc2 MFMAs -- wrong results, timing only
-#endif
 enum { TM_RAMP = 0, TM_STEADY = 1, TM_DRAIN = 2, TM_LAST = 3 };   // LAST = the DRAIN iteration that requests the residual tile
 template <int M> struct ModeC { static constexpr int value = M; };
 template <bool B> struct BoolC { static constexpr bool value = B; };
@@ -164,9 +161,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
     };
     auto issue = [&](const unsigned stoff, const int pi) {
         tm_glds(poff[pi], slice * 7 + pi < 14 ? pb1 : pb2, pdst[pi] + stoff);
-    };
-    auto issue_loop = [&](const unsigned stoff, const int pi) {
-        if (!(TM_ABL & 1) || p.ldxt == 12345) issue(stoff, pi);
     };
     if (role == 0) {
 #pragma unroll
@@ -294,20 +288,16 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
                     for (int j = 0; j < 2; ++j) a1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int kk = 0; kk < TM_KMAX; ++kk) {
-                    issue_loop(stoff2, kk);
+                    issue(stoff2, kk);
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
-                        if constexpr (TM_ABL & 4) {
-                            a1[i][0] += __builtin_bit_cast(f32x4, bw[kk][0]) + __builtin_bit_cast(f32x4, xa[i][kk]);
-                            continue;
-                        }
                         a1[i][0] = Mma2<T>::run(bw[kk][0], xa[i][kk], a1[i][0]);
                         a1[i][1] = Mma2<T>::run(bw[kk][1], xa[i][kk], a1[i][1]);
                     }
                 }
             } else {
 #pragma unroll
-                for (int pi = 0; pi < 7; ++pi) issue_loop(stoff2, pi);
+                for (int pi = 0; pi < 7; ++pi) issue(stoff2, pi);
             }
             if (fc2) {
 #pragma unroll
@@ -324,10 +314,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
                 // natural operands -> lane = token frow of block j, 4 consecutive rows 4*fg + r
 #pragma unroll
                 for (int j = 0; j < TM_NB0; ++j) {
-                    if constexpr (TM_ABL & 8) {
-                        acc2[0][j] += __builtin_bit_cast(f32x4, af0) + __builtin_bit_cast(f32x4, bf[j]);
-                        continue;
-                    }
                     acc2[0][j] = Mma2<T>::run(af0, bf[j], acc2[0][j]);
                     acc2[1][j] = Mma2<T>::run(af1, bf[j], acc2[1][j]);
                 }
@@ -415,13 +401,7 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
                         v[2 * q] = f32x2{a[half * 2 + q].x + bb.x, a[half * 2 + q].y + bb.y};
                         v[2 * q + 1] = f32x2{a[half * 2 + q].z + bb.z, a[half * 2 + q].w + bb.w};
                     }
-#if TM_ABL & 2
-#elif defined(TM_GELU_SCALAR)
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) v[c] = f32x2{gelu16_f<T>(v[c].x), gelu16_f<T>(v[c].y)};
-#else
                     gelu_pk_n<T, 4>(v);
-#endif
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         const int row = half * 16 + frow;
@@ -436,10 +416,6 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
             if (fc2) {
 #pragma unroll
                 for (int j = 0; j < TM_NB1; ++j) {
-                    if constexpr (TM_ABL & 8) {
-                        acc2[0][j] += __builtin_bit_cast(f32x4, af0) + __builtin_bit_cast(f32x4, bf[j]);
-                        continue;
-                    }
                     if (j < TM_NB1 - 1 || blk14) {
                         acc2[0][j] = Mma2<T>::run(af0, bf[j], acc2[0][j]);
                         acc2[1][j] = Mma2<T>::run(af1, bf[j], acc2[1][j]);
@@ -509,12 +485,8 @@ __global__ void __launch_bounds__(512, 1) token_mlp_kernel(const TokenMlpArgs p)
 //     during the 90k-cycle loops.  Touching those lines from inside the loop (LDS-DMA dword loads into a sink, all at once or
 //     one wave per iteration) moved the same wait into the loop's vmcnt and measured slower (0.207-0.218 vs 0.199 ms); left out.
 // LDS: 48 (W1 ring) + 64 (W2 ring) + 32 (epilogue staging) + 4 (b1) + 0.9 (b2) = 149 KiB.
-#ifndef T2_BWD
-#define T2_BWD 3         // W1 fragment pairs read ahead of their MFMAs
-#endif
-#ifndef T2_BFD
-#define T2_BFD 4         // W2 fragments read ahead of their MFMAs
-#endif
+constexpr int T2_BWD = 3;                              // W1 fragment pairs read ahead of their MFMAs
+constexpr int T2_BFD = 4;                              // W2 fragments read ahead of their MFMAs
 constexpr int T2_BM = 256;
 constexpr int T2_NB = 13;                              // token blocks of 16: S <= 208
 constexpr int T2_R1 = 0;
@@ -663,9 +635,7 @@ __global__ void __launch_bounds__(512, 1) token_mlp_rr_kernel(const TokenMlpArgs
         for (int i = 0; i < 2; ++i) {
             f32x2 v[4] = {f32x2{a1[i][0].x + bb0.x, a1[i][0].y + bb0.y}, f32x2{a1[i][0].z + bb0.z, a1[i][0].w + bb0.w},
                           f32x2{a1[i][1].x + bb1.x, a1[i][1].y + bb1.y}, f32x2{a1[i][1].z + bb1.z, a1[i][1].w + bb1.w}};
-#if !(TM_ABL & 2)
             gelu_pk_n<T, 4>(v);
-#endif
             T e[8] = {from_f32<T>(v[0].x), from_f32<T>(v[0].y), from_f32<T>(v[1].x), from_f32<T>(v[1].y),
                       from_f32<T>(v[2].x), from_f32<T>(v[2].y), from_f32<T>(v[3].x), from_f32<T>(v[3].y)};
             __builtin_memcpy(&hf[i], e, 16);
@@ -1596,11 +1566,6 @@ extern "C" int mlpk_token_gemm(int dtype, const void* xt, int ldxt, int M, int S
 }
 
 // mlpk_token_gemm with the LayerNorm / affine of its operand inside (mlpk.h): x token-major, no xt tensor
-extern "C" int mlpk_token_gemm_ln_post(int dtype, const void* x, int ldx, int M, int S, const float* ln_mean, const float* ln_rstd, const float* gamma,
-                                       const float* beta, const void* w, int ldw, const float* bias, int ngroups, const float* rscale, int rperiod,
-                                       const void* R, int ldr, int res_mode, const float* post_scale, const float* post_shift, void* out, int ldo,
-                                       int t_rows, void* stream);
-
 extern "C" int mlpk_token_gemm_ln(int dtype, const void* x, int ldx, int M, int S, const float* ln_mean, const float* ln_rstd, const float* gamma,
                                   const float* beta, const void* w, int ldw, const float* bias, int ngroups, const float* rscale, int rperiod,
                                   const void* R, int ldr, int res_mode, void* out, int ldo, int t_rows, void* stream) {

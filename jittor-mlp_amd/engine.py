@@ -195,7 +195,7 @@ GEMM_PLAN_WHOLE = False
 
 def gemm(A, B, C, M, Nn, K, *, lda=None, ldb=None, ldc=None, bias=None, act=N.ACT_NONE, cscale=None, cshift=None,
          rscale=None, rperiod=0, R=None, ldr=None, res=N.RES_NONE, out_mode=N.OUT_ROWMAJOR, t_rows=0, t_tokens=0,
-         algo=0, tag=None, dbg=0, ln=None, ln_group=1, part=None, prof=None, _defer=False):
+         algo=0, tag=None, dbg=0, ln=None, ln_group=1, part=None, _defer=False):
     """C = epilogue(A . B^T).  `part` = (workspace, name): the epilogue also delivers the row statistics of what it stores
     (mlpk.h: row_part) into a float32 buffer (nparts, M, 2) taken from the workspace; returns (buffer, nparts) for
     stats_finalize_planar, or None when the descriptor cannot deliver them (fp32, unaligned rows) and the caller runs row_stats."""
@@ -224,8 +224,6 @@ def gemm(A, B, C, M, Nn, K, *, lda=None, ldb=None, ldc=None, bias=None, act=N.AC
     d.t_rows, d.t_tokens, d.algo = t_rows, t_tokens, algo
     d.reserved = dbg
     d.workspace, d.workspace_bytes = None, 0             # unused since ABI 5 (no kernel needs scratch)
-    if prof is not None:                                 # -DMLPK_P8_PROF builds: the persistent tile's per-workgroup cycle sums (reserved & 8)
-        d.workspace, d.workspace_bytes = ptr(prof), prof.numel() * prof.element_size()
     out = None
     if part is not None:
         n = ctypes.c_int(0)

@@ -573,6 +573,64 @@ def test_gemm_p8_race_screen_bit_equal_to_s3():
             assert torch.equal(C.view(torch.int16), ref.view(torch.int16)), (M, Nn, K, dbg)
 
 
+def test_gemm_reserved_low_bits_are_ignored():
+    """mlpk.h: every bit of mlpk_gemm_desc.reserved other than 16 / 32 / 64 / 128 is ignored.  Bits 1, 2, 4 and 8 once switched measurement
+    paths on inside the tiles (no K loop, no stores, no epilogue, cycle stamps written through R).  One shape per tile family -- register-staged,
+    direct-to-LDS, s3, persistent, persistent with the statistics epilogue -- with a full-size residual operand: C and the statistics planes
+    have the bits of the reserved = 0 call, R is unchanged, and the guard bands around C and R are intact."""
+    from guard import Guarded, assert_bits_equal
+    pkg = load_pkg()
+    E, N = pkg.engine, pkg._native
+
+    class Planes:                                            # engine.gemm's `part` workspace: a fresh NaN-filled buffer per call
+        def get(self, name, shape, dtype):
+            self.buf = torch.full(shape, float("nan"), dtype=dtype, device=dev())
+            return self.buf
+
+    cases = [  # family, algo, (M, N, K), dtype, epilogue
+        ("register-staged", 1, (130, 70, 136), torch.float32, dict(res=N.RES_ADD)),
+        ("direct-to-LDS", 6, (130, 72, 160), torch.bfloat16, dict(res=N.RES_ADD)),           # N = 72: 16-byte rows, the vector store path
+        # (N = 70 below: the scalar store path.  The persistent GELU case cannot take a residual at M = 320 -- R is passed and must stay
+        #  untouched, but only the statistics case reads it.)
+        ("s3", 11, (130, 70, 160), torch.bfloat16, dict(res=N.RES_ADD)),
+        ("persistent", 14, (320, 256, 128), torch.bfloat16, dict(act=N.ACT_GELU)),
+        ("persistent statistics", 14, (512, 512, 192), torch.bfloat16, dict(res=N.RES_ADD, stats=True)),
+    ]
+    for ci, (family, algo, (M, Nn, K), dtype, epi) in enumerate(cases):
+        A = rnd((M, K), dtype, 700 + ci).to(dev())
+        B = rnd((Nn, K), dtype, 710 + ci, 1.0 / math.sqrt(K)).to(dev())
+        bias = rnd((Nn,), torch.float32, 720 + ci).to(dev())
+        R0 = rnd((M, Nn), dtype, 730 + ci)
+        kw = {k: v for k, v in epi.items() if k != "stats"}
+        want = None
+        for reserved in (0, 1, 2, 4, 8, 15):
+            gc = Guarded(M, Nn, dtype=dtype, device=dev())
+            gr = Guarded(M, Nn, dtype=dtype, device=dev(), role="in", data=R0)
+            planes = Planes()
+            out = E.gemm(A, B, gc.view, M, Nn, K, bias=bias, R=gr.view, algo=algo, dbg=reserved,
+                         part=(planes, "p") if epi.get("stats") else None, **kw)
+            torch.cuda.synchronize()
+            what = "%s, reserved = %d" % (family, reserved)
+            try:
+                gc.check()
+                gr.check()
+            except AssertionError as e:
+                raise AssertionError("%s: %s" % (what, e)) from None
+            got = (gc.dense(), planes.buf.clone() if epi.get("stats") else None)
+            if reserved == 0:
+                assert torch.isfinite(got[0].float()).all(), what
+                ref = gemm_ref(A.cpu(), B.cpu(), M, Nn, K, bias=bias.cpu(), act=kw.get("act", 0), R=R0, res=kw.get("res", 0))
+                err = (got[0].cpu().double() - ref).abs().max().item()
+                assert err < EPS[dtype] * max(1.0, ref.abs().max().item()) * 4, (what, err)
+                if epi.get("stats"):
+                    assert out is not None and out[0] is planes.buf and torch.isfinite(planes.buf).all(), what
+                want = got
+                continue
+            assert_bits_equal(got[0], want[0], what + ": C")
+            if epi.get("stats"):
+                assert_bits_equal(got[1], want[1], what + ": statistics planes")
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("algo", [6, 7, 8, 9, 10, 11, 12, 13])
 def test_gemm_direct_to_lds_tiles(dtype, algo):
