@@ -474,12 +474,7 @@ static int as_conv2_launch(const AsConvArgs& a0, hipStream_t s) {
     a.seg_rows = steps_per_seg * th;
     const int units = a.B * segs;
     const int lds = (th + 4) * Wp * PITCH + 8 * ASC_STG_BYTES + C * 16 + 64;
-    auto k = as_conv2_kernel<T, C, 5, NPRE>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return MLPK_ESHAPE;
-    hipLaunchKernelGGL(k, dim3((unsigned)(units < cus ? units : cus)), dim3(512), lds, s, a);
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(as_conv2_kernel<T, C, 5, NPRE>, dim3((unsigned)(units < cus ? units : cus)), dim3(512), lds, s, a);
 }
 
 }  // namespace mlpk

@@ -479,15 +479,10 @@ template <typename T, int KS1>
 static int cm_launch(const ChanMlpArgs& a, hipStream_t s) {
     using Geo = CmGeo<KS1, 2 * KS1>;
     const bool same = a.R == a.x && a.ldr == a.ldx;
-    auto k = same ? chan_mlp_kernel<T, KS1, 2 * KS1, true> : chan_mlp_kernel<T, KS1, 2 * KS1, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, Geo::LDS);
-    if (e != hipSuccess) return MLPK_ESHAPE;
     const int tiles = (a.M + CM_BM - 1) / CM_BM;
     const int cap = cm_grid_cap() * (same ? CmWgs<T, KS1, true>::value : 1);
     const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), Geo::LDS, s, a);
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(same ? chan_mlp_kernel<T, KS1, 2 * KS1, true> : chan_mlp_kernel<T, KS1, 2 * KS1, false>, dim3(grid), dim3(512), Geo::LDS, s, a);
 }
 
 }  // namespace mlpk

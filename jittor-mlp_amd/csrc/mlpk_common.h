@@ -262,6 +262,25 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 int mlpk_dwconv_direct(int dtype, const void* x, void* out, int B, int H, int W, int C, int k, const float* w,
                        const float* bias, const float* bn_scale, const float* bn_shift, void* stream);
 
+// The one way the library launches a kernel that uses dynamic LDS: raise the kernel's dynamic-LDS limit (more than 64 KiB needs the
+// opt-in; it is set on every launch), launch, and return 0 or the error as MLPK_LAUNCH_CHECK reads it.
+template <typename... Params, typename... Args>
+static inline int launch_lds(void (*kernel)(Params...), dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, const Args&... args) {
+    if (lds_bytes > 0) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, (unsigned)lds_bytes, stream, args...);
+    return (int)hipGetLastError();
+}
+// ... and a generated kernel, which is a code-object symbol with one parameter block (mlpk_gemm_q4.hip, mlpk_tokenmlp_t4.hip)
+static inline int launch_lds(const void* kernel, dim3 grid, dim3 block, int lds_bytes, hipStream_t stream, void* param_block) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return (int)e;
+    e = hipLaunchKernel(kernel, grid, block, &param_block, (size_t)lds_bytes, stream);
+    return e != hipSuccess ? (int)e : (int)hipGetLastError();
+}
+
 #define MLPK_LAUNCH_CHECK()                            \
     do {                                               \
         hipError_t e__ = hipGetLastError();            \

@@ -167,21 +167,9 @@ static int dwconv_lds_launch(int k, const void* x, void* out, int B, int H, int 
     const size_t lds = (size_t)CT * plane * sizeof(T);
     if (lds > 160 * 1024) return DW_NOFIT;              // caller falls back (a value no hipError_t / MLPK_E* takes)
     const dim3 grid((unsigned)B, (unsigned)((C + CT - 1) / CT));
-#define DW_CASE(KS)                                                                                                    \
-    case KS: {                                                                                                         \
-        auto kern = dwconv_lds_kernel<T, KS>;                                                                          \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(DW_NT), lds, s, (const T*)x, (T*)out, B, H, W, C, w, bias, bns, bnh, pitch, plane); \
-        break;                                                                                                         \
-    }
-    switch (k) {
-        DW_CASE(3) DW_CASE(5) DW_CASE(7) DW_CASE(9)
-        default: return DW_NOFIT;                        // other sizes: the generic kernel (odd k <= 13, round 5)
-    }
-#undef DW_CASE
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    if (k != 3 && k != 5 && k != 7 && k != 9) return DW_NOFIT;      // other sizes: the generic kernel (odd k <= 13, round 5)
+    const auto kern = k == 3 ? dwconv_lds_kernel<T, 3> : k == 5 ? dwconv_lds_kernel<T, 5> : k == 7 ? dwconv_lds_kernel<T, 7> : dwconv_lds_kernel<T, 9>;
+    return launch_lds(kern, grid, dim3(DW_NT), (int)lds, s, (const T*)x, (T*)out, B, H, W, C, w, bias, bns, bnh, pitch, plane);
 }
 
 // Sparse-MLP depthwise step (sparse_mlp.py:84-87): out = x + dwconv_same(pre_scale * x + pre_shift) + bias, zero padding
@@ -715,23 +703,16 @@ static int dwconv_mfma_launch(int k, const void* x, void* out, int B, int H, int
     }
     const dim3 grid((unsigned)groups, (unsigned)((B + per - 1) / per));
     const bool full = H == 32 && W == 32 && C % cg == 0;
-    hipError_t e = hipSuccess;
-#define DWM_CASE(KS, CREG)                                                                                              \
-    case KS: {                                                                                                         \
-        constexpr int CR = (CREG) < cpw ? (CREG) : cpw;                                                                \
-        auto kern = full ? dwconv_mfma_kernel<T, KS, cpw, CR, NWV, true> : dwconv_mfma_kernel<T, KS, cpw, CR, NWV, false>; \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-        if (e != hipSuccess) return (int)e;                                                                            \
-        hipLaunchKernelGGL(kern, grid, dim3(NWV * 64), lds, s, (const T*)x, (T*)out, B, H, W, C, w, bias, bns, bnh, per); \
-        break;                                                                                                         \
-    }
+    constexpr int CR7 = DWM_CREG7 < cpw ? DWM_CREG7 : cpw, CR9 = DWM_CREG9 < cpw ? DWM_CREG9 : cpw;
+    decltype(&dwconv_mfma_kernel<T, 3, cpw, 4, NWV, true>) kern;
     switch (k) {
-        DWM_CASE(3, 4) DWM_CASE(5, 4) DWM_CASE(7, DWM_CREG7) DWM_CASE(9, DWM_CREG9)
+        case 3: kern = full ? dwconv_mfma_kernel<T, 3, cpw, 4, NWV, true> : dwconv_mfma_kernel<T, 3, cpw, 4, NWV, false>; break;
+        case 5: kern = full ? dwconv_mfma_kernel<T, 5, cpw, 4, NWV, true> : dwconv_mfma_kernel<T, 5, cpw, 4, NWV, false>; break;
+        case 7: kern = full ? dwconv_mfma_kernel<T, 7, cpw, CR7, NWV, true> : dwconv_mfma_kernel<T, 7, cpw, CR7, NWV, false>; break;
+        case 9: kern = full ? dwconv_mfma_kernel<T, 9, cpw, CR9, NWV, true> : dwconv_mfma_kernel<T, 9, cpw, CR9, NWV, false>; break;
         default: return DW_NOFIT;
     }
-#undef DWM_CASE
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(kern, grid, dim3(NWV * 64), lds, s, (const T*)x, (T*)out, B, H, W, C, w, bias, bns, bnh, per);
 }
 
 extern "C" int mlpk_dwconv_nhwc(int dtype, const void* x, void* out, int B, int H, int W, int C, int k, const float* w,

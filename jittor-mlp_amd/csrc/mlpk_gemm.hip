@@ -17,11 +17,14 @@
 //     residual-add or gate-multiply are applied on the fp32 accumulator before the single store;
 //   * XCD-aware tile order: each of the 8 XCDs walks a contiguous range of tiles (n fastest) so the
 //     A panel and the weight panels are re-used out of that XCD's private L2.
+// Host side (from the "host-side dispatch" banner down): gemm_resolve turns a descriptor into a GemmCall -- arguments, tile,
+// and the launch plan of the tile's pipeline -- and refuses what cannot run; every extern "C" entry point consumes that value.
 #include "mlpk_common.h"
 #include "mlpk_gemm_q4.h"
 #include "mlpk_gemm_skinny.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <utility>
 
 namespace mlpk {
 
@@ -1486,79 +1489,79 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_p8_pair_kernel(const GemmArgs 
 }
 
 // ------------------------------- host-side dispatch -------------------------------
-struct TileCfg { int bm, bn, wm, wn, glds; };
-static const TileCfg kTiles[] = {
-    {256, 256, 2, 4, 0},   // algo 1: 8 waves, 128 KiB LDS, 1 workgroup / CU, register staging
-    {256, 128, 4, 2, 0},   // algo 2: 8 waves,  96 KiB
-    {128, 256, 2, 4, 0},   // algo 3: 8 waves,  96 KiB
-    {128, 128, 2, 2, 0},   // algo 4: 4 waves,  64 KiB, 2 workgroups / CU
-    {64, 64, 2, 2, 0},     // algo 5: 4 waves,  32 KiB, small / ragged problems
-    {256, 256, 2, 4, 1},   // algo 6..9: the same tiles with direct-to-LDS loads (K % half-slab == 0)
-    {256, 128, 4, 2, 1},
-    {128, 256, 2, 4, 1},
-    {128, 128, 2, 2, 1},
-    {64, 64, 2, 2, 1},     // algo 10
-    {256, 128, 2, 2, 2},   // algo 11..13: "s3" pipeline (4 waves, 3 LDS stages of 64-byte rows, 2 workgroups / CU)
-    {128, 128, 2, 2, 2},
-    {128, 256, 2, 2, 2},
-    {256, 256, 2, 4, 3},   // algo 14: "p8" ping-pong pipeline (8 waves, 128 KiB LDS, 1 workgroup / CU; K % slab == 0, K >= 2 slabs)
-    {256, 128, 2, 2, 4},   // algo 15: "q4" generated kernels (mlpk_gemm_q4.hip): 4 waves = one per SIMD, 144 KiB LDS, epilogue of tile
-                           //          T - 1 issued behind the MFMAs of tile T
-    {8, 64, 4, 1, 5},      // algo 16: skinny fp32 kernel (mlpk_gemm_skinny.hip): no MFMA, the whole chip on a product of a few hundred MFLOP
-                           // -- only when asked for (ViP's chain): as an automatic choice it was slower (profiles/r04_skinny_ab.txt)
+// Every entry point resolves its descriptor ONCE (gemm_resolve -> GemmCall: the kernel arguments, the tile, and what the tile's
+// pipeline needs to launch) and then only consumes that value: launching, naming and answering questions about a call cannot
+// disagree, and every refusal happens in gemm_resolve.  Tile geometry, thread count and LDS bytes are stated once, in kTiles:
+// mlpk_gemm_algo_info reads the table, and the template instances a launch picks are generated from the same entries.
+enum { PIPE_REG, PIPE_GLDS, PIPE_S3, PIPE_P8, PIPE_Q4, PIPE_SKINNY };
+struct TileCfg {
+    int bm, bn, wm, wn, pipe;
+    constexpr int threads() const { return wm * wn * 64; }
+    constexpr int lds_bytes() const {
+        return pipe == PIPE_SKINNY ? 6144 : pipe == PIPE_Q4 ? Q4_LDS_BYTES : pipe == PIPE_P8 ? P8_LDS_BYTES : pipe == PIPE_S3 ? 3 * (bm + bn) * 64 : 2 * (bm + bn) * 128;
+    }
+    int tiles(int M, int N) const { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn); }
 };
-static const int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+static constexpr TileCfg kTiles[] = {
+    {256, 256, 2, 4, PIPE_REG},    // algo 1: 8 waves, 128 KiB LDS, 1 workgroup / CU, register staging
+    {256, 128, 4, 2, PIPE_REG},    // algo 2: 8 waves,  96 KiB
+    {128, 256, 2, 4, PIPE_REG},    // algo 3: 8 waves,  96 KiB
+    {128, 128, 2, 2, PIPE_REG},    // algo 4: 4 waves,  64 KiB, 2 workgroups / CU
+    {64, 64, 2, 2, PIPE_REG},      // algo 5: 4 waves,  32 KiB, small / ragged problems
+    {256, 256, 2, 4, PIPE_GLDS},   // algo 6..9: the same tiles with direct-to-LDS loads (K % half-slab == 0)
+    {256, 128, 4, 2, PIPE_GLDS},
+    {128, 256, 2, 4, PIPE_GLDS},
+    {128, 128, 2, 2, PIPE_GLDS},
+    {64, 64, 2, 2, PIPE_GLDS},     // algo 10
+    {256, 128, 2, 2, PIPE_S3},     // algo 11..13: "s3" pipeline (4 waves, 3 LDS stages of 64-byte rows, 2 workgroups / CU)
+    {128, 128, 2, 2, PIPE_S3},     // (algo 12 is also the tile of the implicit convolution, kConvTile)
+    {128, 256, 2, 2, PIPE_S3},
+    {256, 256, 2, 4, PIPE_P8},     // algo 14: "p8" ping-pong pipeline (8 waves, 128 KiB LDS, 1 workgroup / CU; K % slab == 0, K >= 2 slabs)
+    {256, 128, 2, 2, PIPE_Q4},     // algo 15: "q4" generated kernels (mlpk_gemm_q4.hip): 4 waves = one per SIMD, 144 KiB LDS, epilogue of tile
+                                   //          T - 1 issued behind the MFMAs of tile T
+    {8, 64, 4, 1, PIPE_SKINNY},    // algo 16: skinny fp32 kernel (mlpk_gemm_skinny.hip): no MFMA, the whole chip on a product of a few hundred MFLOP
+                                   // -- only when asked for (ViP's chain): as an automatic choice it was slower (profiles/r04_skinny_ab.txt)
+};
+static constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+static constexpr int kNumTemplateTiles = 13;       // algos 1 .. 13 are instances of the gemm_nt / gemm_nt_s3 templates, picked by index below
+static constexpr int kConvTile = 11;
+static_assert(kTiles[kNumTemplateTiles - 1].pipe == PIPE_S3 && kTiles[kNumTemplateTiles].pipe == PIPE_P8 && kTiles[kConvTile].pipe == PIPE_S3, "tile list order");
 
-template <typename T, int BM, int BN, int WM, int WN, bool GLDS>
-static int launch_cfg(const GemmArgs& a, bool trans, hipStream_t stream) {
-    const int lds = 2 * (BM + BN) * 128;
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    hipError_t e;
-    if (trans) {
-        auto k = gemm_nt_kernel<T, BM, BN, WM, WN, true, GLDS>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(WM * WN * 64), lds, stream, a);
-    } else {
-        auto k = gemm_nt_kernel<T, BM, BN, WM, WN, false, GLDS>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(WM * WN * 64), lds, stream, a);
-    }
-    MLPK_LAUNCH_CHECK();
-    return 0;
+typedef void (*GemmKernel)(const GemmArgs);
+typedef void (*GemmPairKernel)(const GemmArgs, const GemmArgs);
+typedef void (*GemmS3PairKernel)(const GemmArgs, const GemmArgs, const int);
+
+template <typename T, int I, bool TRANS> static constexpr GemmKernel tile_instance() {
+    constexpr TileCfg t = kTiles[I];
+    if constexpr (t.pipe == PIPE_S3) return gemm_nt_s3_kernel<T, t.bm, t.bn, t.wm, t.wn, TRANS>;
+    else return gemm_nt_kernel<T, t.bm, t.bn, t.wm, t.wn, TRANS, t.pipe == PIPE_GLDS>;
 }
-
-template <typename T, int BM, int BN, int WM, int WN>
-static int launch_s3(const GemmArgs& a, bool trans, hipStream_t stream) {
-    const int lds = 3 * (BM + BN) * 64;
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    hipError_t e;
-    if (trans) {
-        auto k = gemm_nt_s3_kernel<T, BM, BN, WM, WN, true>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(WM * WN * 64), lds, stream, a);
-    } else {
-        auto k = gemm_nt_s3_kernel<T, BM, BN, WM, WN, false>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(tiles), dim3(WM * WN * 64), lds, stream, a);
-    }
-    MLPK_LAUNCH_CHECK();
-    return 0;
+template <typename T, int I> static constexpr GemmS3PairKernel s3_pair_instance() {
+    constexpr TileCfg t = kTiles[I];
+    if constexpr (t.pipe == PIPE_S3) return gemm_nt_s3_pair_kernel<T, t.bm, t.bn, t.wm, t.wn, false>;
+    else return nullptr;
 }
+template <typename T, int... I> static GemmKernel tile_kernel(int tile, bool trans, std::integer_sequence<int, I...>) {
+    static const GemmKernel k[][2] = {{tile_instance<T, I, false>(), tile_instance<T, I, true>()}...};
+    return k[tile][trans];
+}
+template <typename T, int... I> static GemmS3PairKernel s3_pair_kernel(int tile, std::integer_sequence<int, I...>) {
+    static const GemmS3PairKernel k[] = {s3_pair_instance<T, I>()...};
+    return k[tile];
+}
+typedef std::make_integer_sequence<int, kNumTemplateTiles> TemplateTiles;
 
-template <typename T, int BM, int BN, int WM, int WN>
-static int launch_s3_pair(const GemmArgs& a0, const GemmArgs& a1, hipStream_t stream) {
-    const int lds = 3 * (BM + BN) * 64;
-    const int tiles0 = ((a0.M + BM - 1) / BM) * ((a0.N + BN - 1) / BN), tiles1 = ((a1.M + BM - 1) / BM) * ((a1.N + BN - 1) / BN);
-    auto k = gemm_nt_s3_pair_kernel<T, BM, BN, WM, WN, false>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3(tiles0 + tiles1), dim3(WM * WN * 64), lds, stream, a0, a1, tiles0);
-    MLPK_LAUNCH_CHECK();
-    return 0;
+// the persistent tile's instances: EPI 0 = LDS-staged epilogue (256-row tiles only), 1 = direct, 2 = direct with the by-product row statistics
+template <typename T> static GemmKernel p8_kernel(int epi, int ni) {
+    static const GemmKernel k[2][4] = {
+        {gemm_nt_p8_kernel<T, 1, 1>, gemm_nt_p8_kernel<T, 1, 2>, gemm_nt_p8_kernel<T, 1, 3>, gemm_nt_p8_kernel<T, 1, 4>},
+        {gemm_nt_p8_kernel<T, 2, 1>, gemm_nt_p8_kernel<T, 2, 2>, gemm_nt_p8_kernel<T, 2, 3>, gemm_nt_p8_kernel<T, 2, 4>}};
+    return epi == 0 ? gemm_nt_p8_kernel<T, 0, 4> : k[epi - 1][ni - 1];
+}
+template <typename T> static GemmPairKernel p8_pair_kernel(int epi, int nx) {        // 256-row tiles, then tiles of nx * 64 rows
+    static const GemmPairKernel k[2][3] = {{gemm_nt_p8_pair_kernel<T, 1, 4, 1>, gemm_nt_p8_pair_kernel<T, 1, 4, 2>, gemm_nt_p8_pair_kernel<T, 1, 4, 3>},
+                                           {gemm_nt_p8_pair_kernel<T, 2, 4, 1>, gemm_nt_p8_pair_kernel<T, 2, 4, 2>, gemm_nt_p8_pair_kernel<T, 2, 4, 3>}};
+    return k[epi - 1][nx - 1];
 }
 
 // one persistent workgroup per compute unit (a multiple of 8: whole XCDs)
@@ -1659,87 +1662,66 @@ static bool p8_eligible(const GemmArgs& a, int es, bool trans) {
     return (par & 15) == 0;
 }
 
-template <typename T> static int launch_p8(const GemmArgs& a0, bool trans, hipStream_t stream) {
-    if constexpr (sizeof(T) != 2) {
-        return MLPK_EDTYPE;                  // the persistent tile is a 16-bit kernel (fp32 uses the exact-f32 MFMA tiles)
-    } else {
-        GemmArgs a = a0;
-        if (!p8_eligible(a, 2, trans)) return MLPK_ESHAPE;
-        const int lds = P8_LDS_BYTES;
-        const int tiles_n = a.N / 256;
-        const int cap = p8_grid_cap();
-        a.cgroups = (a.dbg & 128) ? 1 : p8_cgroups(tiles_n, a.K, 2);           // reserved & 128: one column group (A/B runs)
-        // reserved & 64: LDS-staged epilogue (A/B runs); it also serves the rare residual + GELU / residual + LayerNorm
-        // combinations, which the direct epilogue does not instantiate
-        const bool staged = (a.dbg & 64) != 0 || (a.res_mode != MLPK_RES_NONE && (a.act == MLPK_ACT_GELU || a.ln_mean));
-        if (staged && a.M % 256) return MLPK_ESHAPE;                            // the staged epilogue is built for 256-row tiles only
-        const P8Plan plan = p8_plan(a.M, tiles_n, a.K / 64, cap, !staged && !(a.dbg & 16));   // reserved & 16: 256-row tiles only
-        int m_base = 0;
-        auto grid_of = [&](const int panels) {
-            const int X = 8 / a.cgroups;
-            const int U = panels * (tiles_n / a.cgroups);
-            const int Q = (U + X - 1) / X;
-            return 8 * (Q < cap / 8 ? Q : cap / 8);
-        };
-        const bool pair_on = p8_pair_on();
-        for (int s = 0; s < plan.n; ++s) {
-            const int ni = plan.ni[s];
-            a.m_base = m_base;
-            a.panels = plan.panels[s];
-            m_base += a.panels * ni * 64;
-            hipError_t e = hipSuccess;
-            // the 256-row panels of a plan and the shorter ones that follow them (Mixer-B fc2: one round + two rounds of 192-row tiles;
-            // gMLP proj1: nine rounds + a tail of 64-row tiles) go out as one launch
-            const int nj = s + 1 < plan.n ? plan.ni[s + 1] : 0;
-            if (pair_on && !staged && nj && ((ni == 4 && nj < 4) || (nj == 4 && ni < 4))) {
-                GemmArgs b = a;
-                b.m_base = m_base;
-                b.panels = plan.panels[s + 1];
-                m_base += b.panels * nj * 64;
-                const GemmArgs& a4 = ni == 4 ? a : b;
-                const GemmArgs& ax = ni == 4 ? b : a;
-                const int nx = ni == 4 ? nj : ni;
-                const int g4 = grid_of(a4.panels), gx = grid_of(ax.panels);
-                const int gridp = g4 > gx ? g4 : gx;
-#define P8_PAIR(EP, NX)                                                                                                 \
-    {                                                                                                                   \
-        auto k = gemm_nt_p8_pair_kernel<T, EP, 4, NX>;                                                                  \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);     \
-        if (e != hipSuccess) return (int)e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(gridp), dim3(512), lds, stream, a4, ax);                                             \
-    }
-                if (a.row_part) {
-                    if (nx == 3) P8_PAIR(2, 3) else if (nx == 2) P8_PAIR(2, 2) else P8_PAIR(2, 1)
-                } else {
-                    if (nx == 3) P8_PAIR(1, 3) else if (nx == 2) P8_PAIR(1, 2) else P8_PAIR(1, 1)
-                }
-#undef P8_PAIR
-                MLPK_LAUNCH_CHECK();
-                ++s;
-                continue;
-            }
-            const int grid = grid_of(a.panels);
-#define P8_LAUNCH(EP, NIv)                                                                                              \
-    {                                                                                                                   \
-        auto k = gemm_nt_p8_kernel<T, EP, NIv>;                                                                         \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);     \
-        if (e != hipSuccess) return (int)e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, stream, a);                                                   \
-    }
-            if (staged) P8_LAUNCH(0, 4)
-            else if (a.row_part && ni == 4) P8_LAUNCH(2, 4)
-            else if (a.row_part && ni == 3) P8_LAUNCH(2, 3)
-            else if (a.row_part && ni == 2) P8_LAUNCH(2, 2)
-            else if (a.row_part) P8_LAUNCH(2, 1)
-            else if (ni == 4) P8_LAUNCH(1, 4)
-            else if (ni == 3) P8_LAUNCH(1, 3)
-            else if (ni == 2) P8_LAUNCH(1, 2)
-            else P8_LAUNCH(1, 1)
-#undef P8_LAUNCH
-            MLPK_LAUNCH_CHECK();
+// One launch of the persistent tile: the panels [m_base[0], ..) of ni[0] * 64 rows and, when ni[1] != 0, in the same launch
+// the panels [m_base[1], ..) of ni[1] * 64 rows (gemm_nt_p8_pair_kernel: ni[0] == 4, the 256-row tiles are walked first).
+struct P8Step { int ni[2], m_base[2], panels[2], grid; };
+
+// A resolved call: what the dispatch decided for one descriptor.
+struct GemmCall {
+    GemmArgs a;                 // (a.cgroups: the persistent tile's column groups)
+    int dtype, algo;            // algo: 1-based index of `tile` in kTiles
+    const TileCfg* tile;
+    bool trans;
+    // persistent tile: its epilogue (p8_kernel's EPI), the height plan, and the launches that cover it
+    int p8_epi, p8_steps;
+    P8Plan p8_plan;
+    P8Step p8_step[4];
+    Q4Call q4;                  // generated tile
+    const char* q4_name;
+    SkinnyCall skinny;          // skinny kernel
+};
+
+// the launch sequence of the persistent tile for c.a
+static int p8_resolve(GemmCall& c, const P8Plan* mixed_plan) {
+    GemmArgs& a = c.a;
+    const int tiles_n = a.N / 256;
+    const int cap = p8_grid_cap();
+    a.cgroups = (a.dbg & 128) ? 1 : p8_cgroups(tiles_n, a.K, 2);           // reserved & 128: one column group (A/B runs)
+    // reserved & 64: LDS-staged epilogue (A/B runs); it also serves the rare residual + GELU / residual + LayerNorm
+    // combinations, which the direct epilogue does not instantiate
+    const bool staged = (a.dbg & 64) != 0 || (a.res_mode != MLPK_RES_NONE && (a.act == MLPK_ACT_GELU || a.ln_mean));
+    if (staged && a.M % 256) return MLPK_ESHAPE;                            // the staged epilogue is built for 256-row tiles only
+    c.p8_epi = staged ? 0 : a.row_part ? 2 : 1;
+    const bool mixed = !staged && !(a.dbg & 16);                            // reserved & 16: 256-row tiles only
+    // (mixed_plan: the plan the cost model already searched for this call, where it did)
+    c.p8_plan = mixed && mixed_plan ? *mixed_plan : p8_plan(a.M, tiles_n, a.K / 64, cap, mixed);
+    const P8Plan& plan = c.p8_plan;
+    auto grid_of = [&](const int panels) {
+        const int X = 8 / a.cgroups;
+        const int U = panels * (tiles_n / a.cgroups);
+        const int Q = (U + X - 1) / X;
+        return 8 * (Q < cap / 8 ? Q : cap / 8);
+    };
+    const bool pair_on = p8_pair_on();
+    int m_base = 0;
+    c.p8_steps = 0;
+    for (int s = 0; s < plan.n; ++s) {
+        P8Step& st = c.p8_step[c.p8_steps++];
+        st.ni[0] = plan.ni[s]; st.m_base[0] = m_base; st.panels[0] = plan.panels[s];
+        st.ni[1] = st.m_base[1] = st.panels[1] = 0;
+        m_base += st.panels[0] * st.ni[0] * 64;
+        st.grid = grid_of(st.panels[0]);
+        // the 256-row panels of a plan and the shorter ones that follow them (Mixer-B fc2: one round + two rounds of 192-row tiles;
+        // gMLP proj1: nine rounds + a tail of 64-row tiles) go out as one launch (p8_plan lists the heights tallest first)
+        if (pair_on && !staged && st.ni[0] == 4 && s + 1 < plan.n) {
+            ++s;
+            st.ni[1] = plan.ni[s]; st.m_base[1] = m_base; st.panels[1] = plan.panels[s];
+            m_base += st.panels[1] * st.ni[1] * 64;
+            const int g1 = grid_of(st.panels[1]);
+            if (g1 > st.grid) st.grid = g1;
         }
-        return 0;
     }
+    return 0;
 }
 
 // the call as the skinny fp32 kernel takes it (bias, GELU, row-major, nothing else)
@@ -1767,73 +1749,41 @@ static bool q4_call_of(const GemmArgs& a, int dtype, bool trans, Q4Call& c) {
     return q4_supported(c);
 }
 
-template <typename T> static int launch_algo(int algo, const GemmArgs& a, bool trans, hipStream_t s, void* ws, long long ws_bytes) {
-    switch (algo) {
-        case 1: return launch_cfg<T, 256, 256, 2, 4, false>(a, trans, s);
-        case 2: return launch_cfg<T, 256, 128, 4, 2, false>(a, trans, s);
-        case 3: return launch_cfg<T, 128, 256, 2, 4, false>(a, trans, s);
-        case 4: return launch_cfg<T, 128, 128, 2, 2, false>(a, trans, s);
-        case 5: return launch_cfg<T, 64, 64, 2, 2, false>(a, trans, s);
-        case 6: return launch_cfg<T, 256, 256, 2, 4, true>(a, trans, s);
-        case 7: return launch_cfg<T, 256, 128, 4, 2, true>(a, trans, s);
-        case 8: return launch_cfg<T, 128, 256, 2, 4, true>(a, trans, s);
-        case 9: return launch_cfg<T, 128, 128, 2, 2, true>(a, trans, s);
-        case 10: return launch_cfg<T, 64, 64, 2, 2, true>(a, trans, s);
-        case 11: return launch_s3<T, 256, 128, 2, 2>(a, trans, s);
-        case 12: return launch_s3<T, 128, 128, 2, 2>(a, trans, s);
-        case 13: return launch_s3<T, 128, 256, 2, 2>(a, trans, s);
-        case 14: return launch_p8<T>(a, trans, s);
-        case 15: {
-            Q4Call c;
-            if (!q4_call_of(a, dtype_of<T>::value, trans, c)) return MLPK_ESHAPE;
-            return q4_launch(c, s);
-        }
-        case 16: {
-            SkinnyCall c;
-            if (!skinny_call_of(a, dtype_of<T>::value, trans, c)) return MLPK_ESHAPE;
-            return skinny_launch(c, s);
-        }
-        default: return MLPK_EMODE;
-    }
-}
-
 // Pick the tile that minimises (padded MFMA work / tile efficiency) x (a soft tail penalty for grids that
 // do not fill the CUs many times over).  Efficiencies follow the MI355X sweeps in profiles/: with K a
 // multiple of 32 elements the 2-workgroup-per-CU "s3" tiles win on every shape of the path (their
 // epilogue overlaps the other workgroup's main loop); ragged K falls back to the register-staged tiles.
-static int auto_algo(int M, int N, int K, int epc, bool glds_ok, bool p8_ok, bool stats = false) {
+// p8_rounds: the cost of the persistent tile's mixed-height plan (p8_plan), null where that tile cannot take the call.
+static int auto_algo(int M, int N, int K, int epc, bool glds_ok, const double* p8_rounds, bool stats) {
     double best = 1e300;
     int best_algo = 4;
     for (int i = 0; i < kNumTiles; ++i) {
         const TileCfg& t = kTiles[i];
         const int area = t.bm * t.bn;
         if (stats && t.bn < 128) continue;        // the by-product row statistics reduce over whole 16-lane rows = 128 columns
-        if (t.glds >= 4) continue;                // the generated tile / the skinny kernel are chosen in gemm_prepare, not by this cost model
-        if (t.glds == 3) {
+        if (t.pipe >= PIPE_Q4) continue;          // the generated tile / the skinny kernel are chosen in gemm_resolve, not by this cost model
+        if (t.pipe == PIPE_P8) {
             // persistent ping-pong tile: whole launch rounds of one tile per CU, tile heights mixed to fill them (p8_plan);
             // its per-tile fixed cost (first slabs + epilogue, not overlapped with another workgroup) weighs more the
             // shorter K is.  Calibrated on the MI355X sweeps and model benches: 0.76-0.82 x the best s3 time at
             // K = 768 / 3072, break-even around K = 384, behind below that.
-            if (!p8_ok) continue;
+            if (!p8_rounds) continue;
             const double cap = (double)p8_grid_cap();
-            double rounds = 0.0;
-            p8_plan(M, N / 256, K / 64, (int)cap, true, &rounds);
             const double kb = (double)K / epc * 16.0;          // bytes of K per row
             // (round 2: with the direct epilogue and the parameter prefetch the break-even against the s3 tiles moved from
             //  K = 384 down to K = 192: measured 0.164 vs 0.192 ms at K = 256, 0.078 vs 0.078 at 192, 0.054 vs 0.049 at 128,
             //  tools/gemm_sweep.py on the synthetic short-K shapes)
             const double eff = 1.6 * kb / (kb + 260.0);
-            const double cost = rounds * cap * area / eff;
+            const double cost = *p8_rounds * cap * area / eff;
             if (cost < best) { best = cost; best_algo = i + 1; }
             continue;
         }
         if (glds_ok) {
-            if (!(t.glds == 2 || (t.glds == 1 && area <= 64 * 64))) continue;
-        } else if (t.glds != 0) {
+            if (!(t.pipe == PIPE_S3 || (t.pipe == PIPE_GLDS && area <= 64 * 64))) continue;
+        } else if (t.pipe != PIPE_REG) {
             continue;
         }
         const double tiles = (double)((M + t.bm - 1) / t.bm) * (double)((N + t.bn - 1) / t.bn);
-        const double slots = area >= 256 * 256 ? 256.0 : area >= 128 * 128 ? 512.0 : 1024.0;
         // 128 x 256 (wave tile 64 x 128) measured 2-8 % ahead of 256 x 128 on the channel-MLP shapes
         // ... for K > 512; at short K the 256 x 128 tile is the better of the two (K = 128 .. 320: 5-20 % ahead)
         const double wide = K > 512 * (epc / 8.0) ? 1.0 : 0.92, tall = K > 512 * (epc / 8.0) ? 0.97 : 1.0;
@@ -1841,37 +1791,14 @@ static int auto_algo(int M, int N, int K, int epc, bool glds_ok, bool p8_ok, boo
         // (tiles + 256): a soft tail for grids that do not fill the CUs many times over; the same constant for every
         // tile size, so that a problem of a few tiles (the M = batch GEMMs of SplitAttention) is costed by the time of
         // ONE tile, area / eff, and gets the small tile (128 x 128 fp32 tiles took 38 us for 75 MFLOP)
-        (void)slots;
         const double cost = area / eff * (tiles + 256.0);
         if (cost < best) { best = cost; best_algo = i + 1; }
     }
     return best_algo;
 }
 
-}  // namespace mlpk
-
-using namespace mlpk;
-
-extern "C" int mlpk_gemm_algo_count(void) { return kNumTiles; }
-
-extern "C" int mlpk_gemm_algo_info(int algo, int* bm, int* bn, int* threads, int* lds_bytes) {
-    if (algo < 1 || algo > kNumTiles) return MLPK_EMODE;
-    const TileCfg& t = kTiles[algo - 1];
-    if (bm) *bm = t.bm;
-    if (bn) *bn = t.bn;
-    if (threads) *threads = t.wm * t.wn * 64;
-    if (lds_bytes) *lds_bytes = t.glds == 5 ? 6144 : t.glds == 4 ? Q4_LDS_BYTES : t.glds == 3 ? P8_LDS_BYTES : t.glds == 2 ? 3 * (t.bm + t.bn) * 64 : 2 * (t.bm + t.bn) * 128;
-    return 0;
-}
-
-extern "C" long long mlpk_gemm_workspace_bytes(void) {
-    // no kernel needs scratch any more (the split-K hand-over of a partial last round was replaced by mixed tile heights);
-    // the descriptor's workspace fields stay in the ABI and are ignored
-    return 0;
-}
-
-// validation + tile choice shared by mlpk_gemm_nt and mlpk_gemm_row_parts
-static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& trans) {
+// validation, tile choice and the chosen tile's launch plan: the one place that refuses a call
+static int gemm_resolve(const mlpk_gemm_desc* d, GemmCall& c) {
     if (!d) return MLPK_ENULL;
     if (!d->A || !d->B || !d->C) return MLPK_ENULL;
     if (d->dtype != MLPK_F32 && d->dtype != MLPK_F16 && d->dtype != MLPK_BF16) return MLPK_EDTYPE;
@@ -1886,7 +1813,7 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
     if (d->res_mode != MLPK_RES_NONE && !d->R) return MLPK_ENULL;
     if (d->out_mode != MLPK_OUT_ROWMAJOR && d->out_mode != MLPK_OUT_TOKEN_T) return MLPK_EMODE;
     if (d->rscale && d->rperiod <= 0) return MLPK_ESHAPE;
-    trans = d->out_mode == MLPK_OUT_TOKEN_T;
+    const bool trans = c.trans = d->out_mode == MLPK_OUT_TOKEN_T;
     if ((d->ln_mean != nullptr) != (d->ln_rstd != nullptr) || (d->ln_mean != nullptr) != (d->ln_csum != nullptr)) return MLPK_ENULL;
     if (d->ln_mean && trans) return MLPK_EMODE;     // the fold is per GEMM row; token-transposed GEMMs normalise along K
     if (trans) {
@@ -1895,6 +1822,8 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
     } else if (d->ldc < d->N) {
         return MLPK_ESHAPE;
     }
+    GemmArgs& a = c.a;
+    c.dtype = d->dtype;
     a.A = d->A; a.B = d->B; a.C = d->C; a.R = d->R;
     a.bias = d->bias; a.cscale = d->cscale; a.cshift = d->cshift; a.rscale = d->rscale;
     a.ln_mean = d->ln_mean; a.ln_rstd = d->ln_rstd; a.ln_csum = d->ln_csum;
@@ -1919,13 +1848,18 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
         if (d->N % 8 || a.vec_c != 2 || (d->res_mode != MLPK_RES_NONE && a.vec_r != 2)) return MLPK_ESHAPE;
         if ((uintptr_t)d->row_part & 7) return MLPK_EALIGN;
     }
-    algo = d->algo;
+    int algo = d->algo;
     const bool glds_ok = d->K % (4 * epc) == 0;      // K a multiple of half a 128-byte slab
     // the persistent tile is auto-selected where its overlapped epilogue applies (16-bit row-major, no row scale)
-    bool p8_ok = p8_eligible(a, es, trans);
+    const bool p8_can = p8_eligible(a, es, trans);
     // ... and with statistics, where the direct epilogue instantiates them: bias + residual (the GEMMs that produce a residual stream)
     const bool p8_stats_ok = d->res_mode != MLPK_RES_NONE && d->act == MLPK_ACT_NONE && !d->ln_mean && !d->cscale && !d->cshift && !(a.dbg & 64);
-    if (stats && !p8_stats_ok) p8_ok = false;
+    const bool p8_ok = p8_can && (!stats || p8_stats_ok);
+    const bool q4_ok = (algo == 0 || algo == 15) && q4_call_of(a, d->dtype, trans, c.q4);
+    // (only when a generated kernel exists for the call's class: the others fall through to the other tiles, or are refused when asked for)
+    c.q4_name = q4_ok ? q4_variant_name(c.q4) : nullptr;
+    P8Plan mixed_plan;
+    bool have_plan = false;
     if (algo == 0) {
         // round 3: the generated one-wave-per-SIMD tile where it is ahead.  Rule from the per-shape A/B of every GEMM call of the bs=256 models (profiles/r03_gemm_shapes_q4_ab_v1.txt,
         // r03_q4_probe_v3.txt):
@@ -1935,9 +1869,7 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
         //    at N = 768 with short K (0.80-0.87: three column tiles fill the persistent tile's rounds badly), behind elsewhere (short K
         //    with many column tiles 1.05-1.10; K >= 3072 1.10: its LDS-DMA runs two 48-KiB slabs ahead, HBM-latency bound on long K);
         //  * its pipeline spends one extra (draining) block per workgroup: only grids of several tiles per CU.
-        Q4Call qc;
-        // (... and only when a generated kernel exists for the call's class: the others fall through to the other tiles)
-        if (q4_call_of(a, d->dtype, trans, qc) && q4_variant_name(qc)) {
+        if (c.q4_name) {
             const long long tiles = (long long)(d->M / 256) * (d->N / 128);
             bool take = false;
             if (!p8_ok) take = tiles >= 512;
@@ -1946,45 +1878,104 @@ static int gemm_prepare(const mlpk_gemm_desc* d, GemmArgs& a, int& algo, bool& t
             if (take) algo = 15;
         }
     }
-    if (algo == 0) algo = auto_algo(d->M, d->N, d->K, epc, glds_ok, p8_ok, stats);
-    if (algo < 1 || algo > kNumTiles) return MLPK_EMODE;
-    if (kTiles[algo - 1].glds && !glds_ok) return MLPK_ESHAPE;
-    if (kTiles[algo - 1].glds == 4) {
-        Q4Call qc;
-        if (!q4_call_of(a, d->dtype, trans, qc)) return MLPK_ESHAPE;
+    if (algo == 0) {
+        double p8_rounds = 0.0;
+        if (p8_ok) { mixed_plan = p8_plan(d->M, d->N / 256, d->K / 64, p8_grid_cap(), true, &p8_rounds); have_plan = true; }
+        algo = auto_algo(d->M, d->N, d->K, epc, glds_ok, p8_ok ? &p8_rounds : nullptr, stats);
     }
+    if (algo < 1 || algo > kNumTiles) return MLPK_EMODE;
+    const TileCfg& t = kTiles[algo - 1];
+    c.algo = algo;
+    c.tile = &t;
+    if (t.pipe != PIPE_REG && !glds_ok) return MLPK_ESHAPE;
+    if (t.pipe == PIPE_Q4 && !q4_ok) return MLPK_ESHAPE;
     if (stats) {
-        if (kTiles[algo - 1].bn < 128 || (kTiles[algo - 1].glds == 3 && !p8_stats_ok)) return MLPK_EMODE;
+        if (t.bn < 128 || (t.pipe == PIPE_P8 && !p8_stats_ok)) return MLPK_EMODE;
         if (d->row_part_ld < d->M) return MLPK_ESHAPE;
     }
+    switch (t.pipe) {
+        case PIPE_P8:
+            if (es != 2) return MLPK_EDTYPE;     // the persistent tile is a 16-bit kernel (fp32 uses the exact-f32 MFMA tiles)
+            if (!p8_can) return MLPK_ESHAPE;
+            return p8_resolve(c, have_plan ? &mixed_plan : nullptr);
+        case PIPE_Q4: return c.q4_name ? 0 : MLPK_ESHAPE;
+        case PIPE_SKINNY: return skinny_call_of(a, d->dtype, trans, c.skinny) ? 0 : MLPK_ESHAPE;
+        default: return 0;
+    }
+}
+
+template <typename T> static int launch_p8(const GemmCall& c, hipStream_t stream) {
+    for (int s = 0; s < c.p8_steps; ++s) {
+        const P8Step& st = c.p8_step[s];
+        GemmArgs a = c.a, b = c.a;
+        a.m_base = st.m_base[0]; a.panels = st.panels[0];
+        b.m_base = st.m_base[1]; b.panels = st.panels[1];
+        const int rc = st.ni[1] ? launch_lds(p8_pair_kernel<T>(c.p8_epi, st.ni[1]), dim3(st.grid), dim3(512), P8_LDS_BYTES, stream, a, b)
+                                : launch_lds(p8_kernel<T>(c.p8_epi, st.ni[0]), dim3(st.grid), dim3(512), P8_LDS_BYTES, stream, a);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+template <typename T> static int launch_call(const GemmCall& c, hipStream_t s) {
+    const TileCfg& t = *c.tile;
+    switch (t.pipe) {
+        case PIPE_P8:            // (a 16-bit kernel: gemm_resolve refuses fp32, and there are no fp32 instances to pick)
+            if constexpr (sizeof(T) == 2) return launch_p8<T>(c, s);
+            else return MLPK_EDTYPE;
+        case PIPE_Q4: return q4_launch(c.q4, s);
+        case PIPE_SKINNY: return skinny_launch(c.skinny, s);
+        default: return launch_lds(tile_kernel<T>(c.algo - 1, c.trans, TemplateTiles{}), dim3(t.tiles(c.a.M, c.a.N)), dim3(t.threads()), t.lds_bytes(), s, c.a);
+    }
+}
+
+static int gemm_launch(const GemmCall& c, hipStream_t s) {
+    switch (c.dtype) {
+        case MLPK_F32: return launch_call<float>(c, s);
+        case MLPK_F16: return launch_call<f16_t>(c, s);
+        default: return launch_call<bf16_t>(c, s);
+    }
+}
+
+}  // namespace mlpk
+
+using namespace mlpk;
+
+extern "C" int mlpk_gemm_algo_count(void) { return kNumTiles; }
+
+extern "C" int mlpk_gemm_algo_info(int algo, int* bm, int* bn, int* threads, int* lds_bytes) {
+    if (algo < 1 || algo > kNumTiles) return MLPK_EMODE;
+    const TileCfg& t = kTiles[algo - 1];
+    if (bm) *bm = t.bm;
+    if (bn) *bn = t.bn;
+    if (threads) *threads = t.threads();
+    if (lds_bytes) *lds_bytes = t.lds_bytes();
+    return 0;
+}
+
+extern "C" long long mlpk_gemm_workspace_bytes(void) {
+    // no kernel needs scratch any more (the split-K hand-over of a partial last round was replaced by mixed tile heights);
+    // the descriptor's workspace fields stay in the ABI and are ignored
     return 0;
 }
 
 extern "C" int mlpk_gemm_kernel_name(const mlpk_gemm_desc* d, char* buf, int len) {
     if (!d || !buf || len <= 0) return MLPK_ENULL;
-    GemmArgs a;
-    int algo = 0;
-    bool trans = false;
-    const int rc = gemm_prepare(d, a, algo, trans);
+    GemmCall c;
+    const int rc = gemm_resolve(d, c);
     if (rc) return rc;
-    const TileCfg& t = kTiles[algo - 1];
-    if (t.glds == 4) {
-        Q4Call qc;
-        const char* nm = q4_call_of(a, d->dtype, trans, qc) ? q4_variant_name(qc) : nullptr;
-        snprintf(buf, (size_t)len, "%s", nm ? nm : "q4 (no variant)");
-    } else if (t.glds == 3) {
-        // the persistent tile: which template runs follows from the plan of tile heights (launch_p8)
-        const bool staged = (a.dbg & 64) != 0 || (a.res_mode != MLPK_RES_NONE && (a.act == MLPK_ACT_GELU || a.ln_mean));
-        const P8Plan plan = p8_plan(a.M, a.N / 256, a.K / 64, p8_grid_cap(), !staged && !(a.dbg & 16));
-        const bool pair_on = p8_pair_on();
-        const bool pair = pair_on && !staged && plan.n >= 2 && ((plan.ni[0] == 4 && plan.ni[1] < 4) || (plan.ni[1] == 4 && plan.ni[0] < 4));
+    const TileCfg& t = *c.tile;
+    if (t.pipe == PIPE_Q4) {
+        snprintf(buf, (size_t)len, "%s", c.q4_name);
+    } else if (t.pipe == PIPE_P8) {
+        // the persistent tile: the heights of the launch sequence (launch_p8), in plan order
         char hs[32] = "";
-        for (int s = 0, o = 0; s < plan.n && o < 28; ++s) o += snprintf(hs + o, sizeof(hs) - (size_t)o, "%s%d", s ? "+" : "", plan.ni[s] * 64);
-        snprintf(buf, (size_t)len, "%s<EPI=%d> rows %s", pair ? "gemm_nt_p8_pair_kernel" : "gemm_nt_p8_kernel", staged ? 0 : a.row_part ? 2 : 1, hs);
-    } else if (t.glds == 5) {
+        for (int s = 0, o = 0; s < c.p8_plan.n && o < 28; ++s) o += snprintf(hs + o, sizeof(hs) - (size_t)o, "%s%d", s ? "+" : "", c.p8_plan.ni[s] * 64);
+        snprintf(buf, (size_t)len, "%s<EPI=%d> rows %s", c.p8_step[0].ni[1] ? "gemm_nt_p8_pair_kernel" : "gemm_nt_p8_kernel", c.p8_epi, hs);
+    } else if (t.pipe == PIPE_SKINNY) {
         snprintf(buf, (size_t)len, "gemm_skinny_f32_kernel");
     } else {
-        snprintf(buf, (size_t)len, "%s %dx%d", t.glds == 2 ? "gemm_nt_s3_kernel" : t.glds == 1 ? "gemm_nt_glds_kernel" : "gemm_nt_kernel", t.bm, t.bn);
+        snprintf(buf, (size_t)len, "%s %dx%d", t.pipe == PIPE_S3 ? "gemm_nt_s3_kernel" : t.pipe == PIPE_GLDS ? "gemm_nt_glds_kernel" : "gemm_nt_kernel", t.bm, t.bn);
     }
     return 0;
 }
@@ -1995,10 +1986,8 @@ extern "C" int mlpk_gemm_row_parts(const mlpk_gemm_desc* d, int* nparts) {
     alignas(8) float dummy_pair[2];
     if (!q.row_part) q.row_part = dummy_pair;     // a question about the tile choice, nothing is written
     q.row_part_ld = 0x7fffffff;
-    GemmArgs a;
-    int algo = 0;
-    bool trans = false;
-    const int rc = gemm_prepare(&q, a, algo, trans);
+    GemmCall c;
+    const int rc = gemm_resolve(&q, c);
     if (rc) return rc;
     // (round 4: every tile writes planes of 32 columns, reduced in one order -- the answer no longer depends on the tile)
     *nparts = (d->N + 31) / 32;
@@ -2006,17 +1995,9 @@ extern "C" int mlpk_gemm_row_parts(const mlpk_gemm_desc* d, int* nparts) {
 }
 
 extern "C" int mlpk_gemm_nt(const mlpk_gemm_desc* d, void* stream) {
-    GemmArgs a;
-    int algo = 0;
-    bool trans = false;
-    const int rc = gemm_prepare(d, a, algo, trans);
-    if (rc) return rc;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    switch (d->dtype) {
-        case MLPK_F32: return launch_algo<float>(algo, a, trans, s, d->workspace, d->workspace_bytes);
-        case MLPK_F16: return launch_algo<f16_t>(algo, a, trans, s, d->workspace, d->workspace_bytes);
-        default: return launch_algo<bf16_t>(algo, a, trans, s, d->workspace, d->workspace_bytes);
-    }
+    GemmCall c;
+    const int rc = gemm_resolve(d, c);
+    return rc ? rc : gemm_launch(c, reinterpret_cast<hipStream_t>(stream));
 }
 
 // conv_src divides n < n_max by d with one multiply by m = ceil(2^16 / d) and a 16-bit shift: kt / cpk (n_max = kh kw cpk) and tap / kw
@@ -2033,30 +2014,21 @@ extern "C" int mlpk_conv_gemm_nhwc_supported(int dtype, int Cin, int kh, int kw,
            pad < kw && (long long)kh * kw * (Cin / 32) < 65536 && conv_div_exact((long long)kh * kw * (Cin / 32), Cin / 32) && conv_div_exact(kh * kw, kw);
 }
 
-template <typename T>
-static int launch_s3_conv(const GemmArgs& a, hipStream_t stream) {
-    constexpr int BM = 128, BN = 128;
-    const int lds = 3 * (BM + BN) * 64;
-    const int tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    auto k = gemm_nt_s3_conv_kernel<T, BM, BN, 2, 2>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3(tiles), dim3(256), lds, stream, a);
-    MLPK_LAUNCH_CHECK();
-    return 0;
+template <typename T> static int launch_s3_conv(const GemmArgs& a, hipStream_t stream) {
+    constexpr TileCfg t = kTiles[kConvTile];
+    return launch_lds(gemm_nt_s3_conv_kernel<T, t.bm, t.bn, t.wm, t.wn>, dim3(t.tiles(a.M, a.N)), dim3(t.threads()), t.lds_bytes(), stream, a);
 }
 
 // d: the product's descriptor with A = the channel-last (B, H, W, Cin) input (dense pixels), M = B Ho Wo, K = kh kw Cin, lda = K (unused), row-major output
 extern "C" int mlpk_conv_gemm_nhwc(const mlpk_gemm_desc* d, int B, int H, int W, int Cin, int kh, int kw, int stride, int pad, void* stream) {
-    GemmArgs a;
-    int algo = 0;
-    bool trans = false;
-    const int rc = gemm_prepare(d, a, algo, trans);
+    GemmCall c;
+    const int rc = gemm_resolve(d, c);
     if (rc) return rc;
-    if (B <= 0 || H <= 0 || W <= 0 || !mlpk_conv_gemm_nhwc_supported(d->dtype, Cin, kh, kw, stride, pad) || trans) return MLPK_ESHAPE;
+    if (B <= 0 || H <= 0 || W <= 0 || !mlpk_conv_gemm_nhwc_supported(d->dtype, Cin, kh, kw, stride, pad) || c.trans) return MLPK_ESHAPE;
     if (H + 2 * pad < kh || W + 2 * pad < kw) return MLPK_ESHAPE;
     const int Ho = (H + 2 * pad - kh) / stride + 1, Wo = (W + 2 * pad - kw) / stride + 1;
     if ((long long)B * Ho * Wo != d->M || (long long)kh * kw * Cin != d->K || d->N % 8) return MLPK_ESHAPE;
+    GemmArgs& a = c.a;
     a.cv_H = H; a.cv_W = W; a.cv_Cin = Cin; a.cv_kw = kw; a.cv_cpk = Cin / 32; a.cv_stride = stride; a.cv_pad = pad; a.cv_Ho = Ho; a.cv_Wo = Wo;
     a.cv_inv_cpk = (65536 + a.cv_cpk - 1) / a.cv_cpk;      // kt / cpk for kt < 65536 / cpk by one multiply
     a.cv_inv_kw = (65536 + kw - 1) / kw;
@@ -2066,28 +2038,20 @@ extern "C" int mlpk_conv_gemm_nhwc(const mlpk_gemm_desc* d, int B, int H, int W,
 
 // two products in one launch where the dispatch gives both the same "s3" tile (row-major outputs, 16-bit); anything else: one after the other
 extern "C" int mlpk_gemm_nt_pair(const mlpk_gemm_desc* d0, const mlpk_gemm_desc* d1, void* stream) {
-    GemmArgs a0, a1;
-    int algo0 = 0, algo1 = 0;
-    bool t0 = false, t1 = false;
-    int rc = gemm_prepare(d0, a0, algo0, t0);
+    GemmCall c0, c1;
+    int rc = gemm_resolve(d0, c0);
     if (rc) return rc;
-    rc = gemm_prepare(d1, a1, algo1, t1);
+    rc = gemm_resolve(d1, c1);
     if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (algo0 == algo1 && algo0 >= 11 && algo0 <= 13 && !t0 && !t1 && d0->dtype == d1->dtype && d0->dtype != MLPK_F32 &&
-        !(a0.dbg | a1.dbg)) {
-#define MLPK_PAIR(TT)                                                                  \
-    switch (algo0) {                                                                   \
-        case 11: return launch_s3_pair<TT, 256, 128, 2, 2>(a0, a1, s);                 \
-        case 12: return launch_s3_pair<TT, 128, 128, 2, 2>(a0, a1, s);                 \
-        default: return launch_s3_pair<TT, 128, 256, 2, 2>(a0, a1, s);                 \
+    const TileCfg& t = *c0.tile;
+    if (c0.tile == c1.tile && t.pipe == PIPE_S3 && !c0.trans && !c1.trans && c0.dtype == c1.dtype && c0.dtype != MLPK_F32 && !(c0.a.dbg | c1.a.dbg)) {
+        const GemmS3PairKernel k = c0.dtype == MLPK_F16 ? s3_pair_kernel<f16_t>(c0.algo - 1, TemplateTiles{}) : s3_pair_kernel<bf16_t>(c0.algo - 1, TemplateTiles{});
+        const int tiles0 = t.tiles(c0.a.M, c0.a.N), tiles1 = t.tiles(c1.a.M, c1.a.N);
+        return launch_lds(k, dim3(tiles0 + tiles1), dim3(t.threads()), t.lds_bytes(), s, c0.a, c1.a, tiles0);
     }
-        if (d0->dtype == MLPK_F16) { MLPK_PAIR(f16_t) } else { MLPK_PAIR(bf16_t) }
-#undef MLPK_PAIR
-    }
-    rc = mlpk_gemm_nt(d0, stream);
-    if (rc) return rc;
-    return mlpk_gemm_nt(d1, stream);
+    rc = gemm_launch(c0, s);
+    return rc ? rc : gemm_launch(c1, s);
 }
 
 extern "C" int mlpk_gemm_set_plan(int mode) {

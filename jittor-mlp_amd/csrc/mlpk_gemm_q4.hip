@@ -120,13 +120,7 @@ int q4_launch(const Q4Call& c, hipStream_t stream) {
     a.prof = nullptr;
     a.row_part = c.row_part; a.row_part_ld = c.row_part_ld;
     a.pad[0] = a.pad[1] = a.pad[2] = 0;
-    hipError_t e = hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, Q4_LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    void* params[] = {&a};
-    e = hipLaunchKernel(v->fn, dim3(grid), dim3(256), params, Q4_LDS_BYTES, stream);
-    if (e != hipSuccess) return (int)e;
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(v->fn, dim3(grid), dim3(256), Q4_LDS_BYTES, stream, &a);
 }
 
 }  // namespace mlpk

@@ -593,13 +593,16 @@ __global__ void __launch_bounds__(256) mixshift_k1_kernel(const MixShiftArgs p, 
     out[(img + (size_t)y * p.W + xx) * p.C + c] = from_f32<T>(acc);
 }
 
+// 0 = launched, MT_NOT_TAKEN = shape outside these kernels (the next kernel in line takes it; distinct from every hipError_t >= 0 and MLPK_E* value),
+// else a HIP error
+constexpr int MT_NOT_TAKEN = -1000;
 template <typename T>
 static int mixshift_band_launch(const MixShiftArgs& a, hipStream_t s) {
     constexpr int EPV = 16 / (int)sizeof(T);
     const int strips = (a.W + 7) / 8;
-    if (strips > MS_TMAX) return 1;
+    if (strips > MS_TMAX) return MT_NOT_TAKEN;
     for (int g = 0; g < a.groups; ++g)
-        if (a.ksize[g] != 1 && a.ksize[g] != 3 && a.ksize[g] != 5 && a.ksize[g] != 7) return 1;
+        if (a.ksize[g] != 1 && a.ksize[g] != 3 && a.ksize[g] != 5 && a.ksize[g] != 7) return MT_NOT_TAKEN;
     const int nbands = (a.H + MS_R - 1) / MS_R;
     for (int g = 0; g < a.groups; ++g) {
         const int k = a.ksize[g], P = k / 2;
@@ -623,21 +626,13 @@ static int mixshift_band_launch(const MixShiftArgs& a, hipStream_t s) {
         plane = (plane + EPV - 1) / EPV * EPV;
         if (((plane / EPV) & 1) == 0) plane += EPV;            // odd number of 16-byte slots per channel plane: conflict-free across channels
         const size_t lds = (size_t)MS_CT * plane * sizeof(T);
-        if (lds > 150 * 1024) return 1;
+        if (lds > 150 * 1024) return MT_NOT_TAKEN;
         int sh = a.shift[g] % a.H, sw = a.shift[g] % a.W;
         if (sh < 0) sh += a.H;
         if (sw < 0) sw += a.W;
         const dim3 grid((unsigned)(a.B * nbands), (unsigned)((cn + MS_CT - 1) / MS_CT));
-#define MS_CASE(KS)                                                                                                         \
-    case KS: {                                                                                                              \
-        auto kern = mixshift_band_kernel<T, KS>;                                                                            \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                                                 \
-        hipLaunchKernelGGL(kern, grid, dim3(MS_NT), lds, s, a, cb, cn, sh, sw, pitch, plane);                                \
-        break;                                                                                                              \
-    }
-        switch (k) { MS_CASE(1) MS_CASE(3) MS_CASE(5) MS_CASE(7) default: return 1; }
-#undef MS_CASE
+        const auto kern = k == 1 ? mixshift_band_kernel<T, 1> : k == 3 ? mixshift_band_kernel<T, 3> : k == 5 ? mixshift_band_kernel<T, 5> : mixshift_band_kernel<T, 7>;
+        if (const int rc = launch_lds(kern, grid, dim3(MS_NT), (int)lds, s, a, cb, cn, sh, sw, pitch, plane)) return rc;
     }
     return 0;
 }
@@ -883,9 +878,7 @@ __global__ void __launch_bounds__(MT_NT) mixshift_tile_kernel(const MixShiftArgs
     }
 }
 
-// 0 = launched, MT_NOT_TAKEN = shape outside this kernel (the per-chunk band kernel / the gather kernels take it; distinct from every hipError_t >= 0
-// and MLPK_E* value), else a HIP error
-constexpr int MT_NOT_TAKEN = -1000;
+// (returns as mixshift_band_launch: MT_NOT_TAKEN = the per-chunk band kernel / the gather kernels take the shape)
 template <typename T>
 static int mixshift_tile_launch(const MixShiftArgs& a, hipStream_t s, float* row_part = nullptr, long long row_part_ld = 0, bool query = false) {
     if (sizeof(T) != 2 || (a.C & 7) || (!query && (((uintptr_t)a.x | (uintptr_t)a.out) & 15))) return MT_NOT_TAKEN;
@@ -924,12 +917,8 @@ static int mixshift_tile_launch(const MixShiftArgs& a, hipStream_t s, float* row
     const int nbands = (a.H + R - 1) / R;
     if ((long long)a.B * nbands > 0x7fffffffll) return MT_NOT_TAKEN;
     if (query) return 0;
-    auto kern = mixshift_tile_kernel<T>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
     const dim3 grid((unsigned)(a.B * nbands), (unsigned)((a.C + MT_CB - 1) / MT_CB));
-    hipLaunchKernelGGL(kern, grid, dim3(MT_NT), lds, s, a, R, pitch, plane, nbands, row_part, row_part_ld);
-    return 0;
+    return launch_lds(mixshift_tile_kernel<T>, grid, dim3(MT_NT), (int)lds, s, a, R, pitch, plane, nbands, row_part, row_part_ld);
 }
 
 // ================================ Swin-MLP: the whole spatial-MLP half of a block in one kernel ================================
@@ -1354,50 +1343,21 @@ extern "C" int mlpk_swin_spatial_stats(int dtype, void* x, int B, int H, int W, 
     const int lds = lds_t > lds_o ? lds_t : lds_o;
     if (lds > 160 * 1024) return MLPK_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipError_t e = hipSuccess;
     const int items = (t2 * (C / 8) + SW_NT - 1) / SW_NT, hpw = (heads + 3) / 4;
+    const bool bf = dtype == MLPK_BF16;
+    void (*k)(const SwinArgs);
     const char* q_env = getenv("MLPK_SWIN_SPATIAL_Q");                 // test hook, read per call: "0" = the round-4 kernel (the bit-equality test)
     if (!(q_env && q_env[0] == '0')) {
         const int qitems = (((t2 + 3) / 4) * (C / 8) + SW_NT - 1) / SW_NT;
-#define SWQ_LAUNCH(TT, MAXQ, NHW)                                                                                          \
-    do {                                                                                                                   \
-        auto k = swin_spatial_q_kernel<TT, MAXQ, NHW>;                                                                     \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);        \
-        if (e != hipSuccess) return (int)e;                                                                                \
-        hipLaunchKernelGGL(k, dim3((unsigned)nwin), dim3(SW_NT), lds, s, a);                                               \
-    } while (0)
-#define SWQ_PICK(TT)                                                                                                       \
-    do {                                                                                                                   \
-        if (qitems <= 1 && hpw <= 1) SWQ_LAUNCH(TT, 1, 1);                                                                 \
-        else if (qitems <= 2 && hpw <= 2) SWQ_LAUNCH(TT, 2, 2);                                                            \
-        else if (qitems <= 3 && hpw <= 3) SWQ_LAUNCH(TT, 3, 3);                                                            \
-        else SWQ_LAUNCH(TT, 6, 6);                                                                                         \
-    } while (0)
-        if (dtype == MLPK_BF16) SWQ_PICK(bf16_t); else SWQ_PICK(f16_t);
-#undef SWQ_PICK
-#undef SWQ_LAUNCH
-        MLPK_LAUNCH_CHECK();
-        return 0;
-    }
-#define SW_LAUNCH(TT, MAXI, NHW)                                                                                           \
-    do {                                                                                                                   \
-        auto k = swin_spatial_kernel<TT, MAXI, NHW>;                                                                       \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);        \
-        if (e != hipSuccess) return (int)e;                                                                                \
-        hipLaunchKernelGGL(k, dim3((unsigned)nwin), dim3(SW_NT), lds, s, a);                                               \
-    } while (0)
-#define SW_PICK(TT)                                                                                                        \
-    do {                                                                                                                   \
-        if (items <= 3 && hpw <= 1) SW_LAUNCH(TT, 3, 1);                                                                   \
-        else if (items <= 5 && hpw <= 2) SW_LAUNCH(TT, 5, 2);                                                              \
-        else if (items <= 10 && hpw <= 3) SW_LAUNCH(TT, 10, 3);                                                            \
-        else SW_LAUNCH(TT, SW_MAXI, 6);                                                                                    \
-    } while (0)
-    if (dtype == MLPK_BF16) SW_PICK(bf16_t); else SW_PICK(f16_t);
-#undef SW_PICK
-#undef SW_LAUNCH
-    MLPK_LAUNCH_CHECK();
-    return 0;
+        if (qitems <= 1 && hpw <= 1) k = bf ? swin_spatial_q_kernel<bf16_t, 1, 1> : swin_spatial_q_kernel<f16_t, 1, 1>;
+        else if (qitems <= 2 && hpw <= 2) k = bf ? swin_spatial_q_kernel<bf16_t, 2, 2> : swin_spatial_q_kernel<f16_t, 2, 2>;
+        else if (qitems <= 3 && hpw <= 3) k = bf ? swin_spatial_q_kernel<bf16_t, 3, 3> : swin_spatial_q_kernel<f16_t, 3, 3>;
+        else k = bf ? swin_spatial_q_kernel<bf16_t, 6, 6> : swin_spatial_q_kernel<f16_t, 6, 6>;
+    } else if (items <= 3 && hpw <= 1) k = bf ? swin_spatial_kernel<bf16_t, 3, 1> : swin_spatial_kernel<f16_t, 3, 1>;
+    else if (items <= 5 && hpw <= 2) k = bf ? swin_spatial_kernel<bf16_t, 5, 2> : swin_spatial_kernel<f16_t, 5, 2>;
+    else if (items <= 10 && hpw <= 3) k = bf ? swin_spatial_kernel<bf16_t, 10, 3> : swin_spatial_kernel<f16_t, 10, 3>;
+    else k = bf ? swin_spatial_kernel<bf16_t, SW_MAXI, 6> : swin_spatial_kernel<f16_t, SW_MAXI, 6>;
+    return launch_lds(k, dim3((unsigned)nwin), dim3(SW_NT), lds, s, a);
 }
 
 static int mixshift_args(mlpk::MixShiftArgs& a, int dtype, const void* x, void* out, int B, int H, int W, int C, int groups, const int* shift, const int* ksize,
@@ -1439,10 +1399,7 @@ extern "C" int mlpk_mixshift_nhwc_stats(int dtype, const void* x, void* out, int
     if (rc) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     rc = dtype == MLPK_F16 ? mlpk::mixshift_tile_launch<mlpk::f16_t>(a, s, row_part, row_part_ld) : mlpk::mixshift_tile_launch<mlpk::bf16_t>(a, s, row_part, row_part_ld);
-    if (rc == mlpk::MT_NOT_TAKEN) return MLPK_ESHAPE;        // ask mlpk_mixshift_stats_planes first
-    if (rc) return rc;
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return rc == mlpk::MT_NOT_TAKEN ? MLPK_ESHAPE : rc;       // ask mlpk_mixshift_stats_planes first
 }
 
 extern "C" int mlpk_mixshift_nhwc(int dtype, const void* x, void* out, int B, int H, int W, int C, int groups, const int* shift,
@@ -1459,11 +1416,7 @@ extern "C" int mlpk_mixshift_nhwc(int dtype, const void* x, void* out, int B, in
     const char* tile_env = getenv("MLPK_MIXSHIFT_TILE");       // test hook, read per call: "0" = the per-chunk band kernel (the bit-equality test)
     if (!(tile_env && tile_env[0] == '0') && dtype != MLPK_F32) {
         const int rc = dtype == MLPK_F16 ? mlpk::mixshift_tile_launch<mlpk::f16_t>(a, s) : mlpk::mixshift_tile_launch<mlpk::bf16_t>(a, s);
-        if (rc != mlpk::MT_NOT_TAKEN) {
-            if (rc) return rc;
-            MLPK_LAUNCH_CHECK();
-            return 0;
-        }
+        if (rc != mlpk::MT_NOT_TAKEN) return rc;
     }
     if (B <= 0x7fffff) {
         int rc;
@@ -1472,9 +1425,9 @@ extern "C" int mlpk_mixshift_nhwc(int dtype, const void* x, void* out, int B, in
             case MLPK_F16: rc = mlpk::mixshift_band_launch<mlpk::f16_t>(a, s); break;
             default: rc = mlpk::mixshift_band_launch<mlpk::bf16_t>(a, s); break;
         }
-        if (rc != 1) {                                      // 1 = shape outside the tiled kernel: gather kernels below
+        if (rc != mlpk::MT_NOT_TAKEN) {                     // (not taken = shape outside the tiled kernel: gather kernels below)
             if (rc) return rc;
-            MLPK_LAUNCH_CHECK();
+            MLPK_LAUNCH_CHECK();                            // (the k = 1 chunks launch without dynamic LDS)
             return 0;
         }
     }

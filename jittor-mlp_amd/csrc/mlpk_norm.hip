@@ -949,22 +949,9 @@ extern "C" int mlpk_norm_apply(const mlpk_norm_desc* d, void* stream) {
         a.ld_sum = d->ld_sum;
         const unsigned grid = (unsigned)(a.B * (which == 0 ? d->W : d->H));
         const size_t bytes = lds[which];
-        if (fast[which]) {
-            DISPATCH_DTYPE(d->dtype, {
-                auto k = vip_permute_fast_kernel<T>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-                if (e != hipSuccess) return (int)e;
-                hipLaunchKernelGGL(k, dim3(grid), dim3(256), bytes, s, a);
-            });
-        } else {
-            DISPATCH_DTYPE(d->dtype, {
-                auto k = vip_permute_kernel<T>;
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-                if (e != hipSuccess) return (int)e;
-                hipLaunchKernelGGL(k, dim3(grid), dim3(256), bytes, s, a);
-            });
-        }
-        MLPK_LAUNCH_CHECK();
+        int rc = 0;
+        DISPATCH_DTYPE(d->dtype, rc = launch_lds(fast[which] ? vip_permute_fast_kernel<T> : vip_permute_kernel<T>, dim3(grid), dim3(256), (int)bytes, s, a));
+        if (rc) return rc;
     }
     return 0;
 }
@@ -981,22 +968,13 @@ extern "C" int mlpk_layernorm_transpose(int dtype, const void* x, int64_t nimg, 
     if (nimg * a.s_tiles > 0x7fffffffLL) return MLPK_ESHAPE;
     const size_t lds = (size_t)(C / 2) * 34 * 4;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define LNTT_LAUNCH(TT, NV, LP)                                                                                          \
-    {                                                                                                                    \
-        auto k = layernorm_transpose_kernel<TT, NV, LP>;                                                                 \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        if (e != hipSuccess) return (int)e;                                                                              \
-        hipLaunchKernelGGL(k, dim3((unsigned)(nimg * a.s_tiles)), dim3(32 * LP), lds, s, a);                             \
-    }
     const bool wide32 = C > 1024 && C % 256 == 0;           // 32 lanes per token
-    if (dtype == MLPK_BF16) {
-        if (C <= 1024) LNTT_LAUNCH(bf16_t, 8, 16) else if (wide32) LNTT_LAUNCH(bf16_t, 8, 32) else LNTT_LAUNCH(bf16_t, 16, 16)
-    } else {
-        if (C <= 1024) LNTT_LAUNCH(f16_t, 8, 16) else if (wide32) LNTT_LAUNCH(f16_t, 8, 32) else LNTT_LAUNCH(f16_t, 16, 16)
-    }
-#undef LNTT_LAUNCH
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    const bool bf = dtype == MLPK_BF16;
+    void (*k)(LnTtArgs);
+    if (C <= 1024) k = bf ? layernorm_transpose_kernel<bf16_t, 8, 16> : layernorm_transpose_kernel<f16_t, 8, 16>;
+    else if (wide32) k = bf ? layernorm_transpose_kernel<bf16_t, 8, 32> : layernorm_transpose_kernel<f16_t, 8, 32>;
+    else k = bf ? layernorm_transpose_kernel<bf16_t, 16, 16> : layernorm_transpose_kernel<f16_t, 16, 16>;
+    return launch_lds(k, dim3((unsigned)(nimg * a.s_tiles)), dim3(wide32 ? 1024 : 512), (int)lds, s, a);
 }
 
 extern "C" int mlpk_vip_unpermute(int dtype, int which, const void* z, void* out, int B, int H, int W, int C,
@@ -1010,13 +988,7 @@ extern "C" int mlpk_vip_unpermute(int dtype, int which, const void* z, void* out
     if (lds > 160 * 1024) return MLPK_ESHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(B * (which == 0 ? W : H));
-    DISPATCH_DTYPE(dtype, {
-        auto k = vip_unpermute_kernel<T>;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, s, (const T*)z, (T*)out, B, H, W, C, seg, ldz, which);
-    });
-    MLPK_LAUNCH_CHECK();
+    DISPATCH_DTYPE(dtype, return launch_lds(vip_unpermute_kernel<T>, dim3(grid), dim3(256), (int)lds, s, (const T*)z, (T*)out, B, H, W, C, seg, ldz, which));
     return 0;
 }
 

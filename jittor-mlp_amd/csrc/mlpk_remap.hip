@@ -827,23 +827,12 @@ extern "C" int mlpk_norm_shift_nhwc(int dtype, const void* in, void* out_w, void
     const size_t img_bytes = (size_t)H * W * C * 2;
     const size_t img_lds = img_bytes + (size_t)C * 8;                // + the per-channel scale / shift tables
     if (img_lds <= 160 * 1024 && (size_t)H * W * (C / 8) < (1u << 17)) {
-        hipError_t e = hipSuccess;
-#define NSI_LAUNCH(TT, GG)                                                                                                              \
-    {                                                                                                                                   \
-        auto k = norm_shift_img_kernel<TT, GG>;                                                                                         \
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)img_lds);           \
-        if (e != hipSuccess) return (int)e;                                                                                             \
-        hipLaunchKernelGGL(k, dim3(N), dim3(512), img_lds, s, (const TT*)in, (TT*)out_w, (TT*)out_h, H, W, C, kernel_size, mean, rstd, gamma, beta); \
-    }
-        const bool gelu = act == MLPK_ACT_GELU;
-        if (dtype == MLPK_BF16) {
-            if (gelu) NSI_LAUNCH(bf16_t, true) else NSI_LAUNCH(bf16_t, false)
-        } else {
-            if (gelu) NSI_LAUNCH(f16_t, true) else NSI_LAUNCH(f16_t, false)
-        }
-#undef NSI_LAUNCH
-        MLPK_LAUNCH_CHECK();
-        return 0;
+        auto go = [&](auto t) {
+            typedef decltype(t) TT;
+            return launch_lds(act == MLPK_ACT_GELU ? norm_shift_img_kernel<TT, true> : norm_shift_img_kernel<TT, false>, dim3(N), dim3(512), (int)img_lds, s,
+                              (const TT*)in, (TT*)out_w, (TT*)out_h, H, W, C, kernel_size, mean, rstd, gamma, beta);
+        };
+        return dtype == MLPK_BF16 ? go(bf16_t{}) : go(f16_t{});
     }
     if (dtype == MLPK_BF16) {
         hipLaunchKernelGGL((norm_shift_vec_kernel<bf16_t>), dim3(grid_for(total / 8)), dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out_w,
@@ -989,20 +978,8 @@ extern "C" int mlpk_vip_split_apply(int dtype, const void* zh, const void* zw, c
     if (H % 8 == 0 && W % 8 == 0 && ldh % 8 == 0 && ldw % 8 == 0 && lds_tile <= 150 * 1024 && (int64_t)B * (H / 8) * (W / 8) * parts < 0x7fffffff &&
         (((uintptr_t)zh | (uintptr_t)zw) & 15) == 0) {
         const unsigned grid = (unsigned)((int64_t)B * (H / 8) * (W / 8) * parts);
-        hipError_t e = hipSuccess;
-        if (dtype == MLPK_BF16) {
-            auto k = vip_split_apply_tile_kernel<bf16_t>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds_tile, s, p, bar, (bf16_t*)out, ldo, parts);
-        } else {
-            auto k = vip_split_apply_tile_kernel<f16_t>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile);
-            if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds_tile, s, p, bar, (f16_t*)out, ldo, parts);
-        }
-        MLPK_LAUNCH_CHECK();
-        return 0;
+        if (dtype == MLPK_BF16) return launch_lds(vip_split_apply_tile_kernel<bf16_t>, dim3(grid), dim3(512), (int)lds_tile, s, p, bar, (bf16_t*)out, ldo, parts);
+        return launch_lds(vip_split_apply_tile_kernel<f16_t>, dim3(grid), dim3(512), (int)lds_tile, s, p, bar, (f16_t*)out, ldo, parts);
     }
     if (dtype == MLPK_BF16) hipLaunchKernelGGL((vip_split_apply_kernel<bf16_t>), dim3(grid_for(total / 8)), dim3(256), 0, s, p, bar, (bf16_t*)out, ldo);
     else hipLaunchKernelGGL((vip_split_apply_kernel<f16_t>), dim3(grid_for(total / 8)), dim3(256), 0, s, p, bar, (f16_t*)out, ldo);

@@ -313,22 +313,10 @@ static int smlp_launch(int dtype, SmlpArgs& a, bool dw, hipStream_t s) {
     const int per_cu = lds <= 78 * 1024 ? 2 : 1;
     const int grid = units < cu * per_cu ? units : cu * per_cu;
     const bool small = H * W * 4 <= SM_NL_SMALL * SM_NT;     // few pieces per thread: the short unrolling (no spills)
-#define SM_LAUNCH(TT, DD)                                                                                               \
-    if (small) SM_LAUNCH2(TT, DD, SM_NL_SMALL) else SM_LAUNCH2(TT, false, 8)
-#define SM_LAUNCH2(TT, DD, NN)                                                                                          \
-    {                                                                                                                   \
-        auto k = smlp_mix_kernel<TT, DD, NN>;                                                                           \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-        if (e != hipSuccess) return (int)e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(SM_NT), lds, s, a);                                                      \
-    }
-    if (dtype == MLPK_BF16) {
-        if (dw) SM_LAUNCH(bf16_t, true) else SM_LAUNCH(bf16_t, false)
-    } else {
-        if (dw) SM_LAUNCH(f16_t, true) else SM_LAUNCH(f16_t, false)
-    }
-#undef SM_LAUNCH
-#undef SM_LAUNCH2
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    const bool bf = dtype == MLPK_BF16;
+    void (*k)(const SmlpArgs);
+    if (!small) k = bf ? smlp_mix_kernel<bf16_t, false, 8> : smlp_mix_kernel<f16_t, false, 8>;
+    else if (dw) k = bf ? smlp_mix_kernel<bf16_t, true, SM_NL_SMALL> : smlp_mix_kernel<f16_t, true, SM_NL_SMALL>;
+    else k = bf ? smlp_mix_kernel<bf16_t, false, SM_NL_SMALL> : smlp_mix_kernel<f16_t, false, SM_NL_SMALL>;
+    return launch_lds(k, dim3(grid), dim3(SM_NT), lds, s, a);
 }

@@ -1439,37 +1439,11 @@ extern "C" int mlpk_token_mlp(int dtype, const void* xt, int ldxt, int M, int S,
         if ((unsigned long long)M * ldxt * 2ull >= (1ull << 32)) return MLPK_ESHAPE;                // ... and into xt (prefetch)
         const int tiles2 = (M + T2_BM - 1) / T2_BM;
         const unsigned grid2 = (unsigned)(tiles2 < tm_grid_cap() ? tiles2 : tm_grid_cap());
-        hipError_t e2;
-        if (dtype == MLPK_BF16) {
-            auto k = token_mlp_rr_kernel<bf16_t>;
-            e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS);
-            if (e2 != hipSuccess) return (int)e2;
-            hipLaunchKernelGGL(k, dim3(grid2), dim3(512), T2_LDS, s, a);
-        } else {
-            auto k = token_mlp_rr_kernel<f16_t>;
-            e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, T2_LDS);
-            if (e2 != hipSuccess) return (int)e2;
-            hipLaunchKernelGGL(k, dim3(grid2), dim3(512), T2_LDS, s, a);
-        }
-        MLPK_LAUNCH_CHECK();
-        return 0;
+        return launch_lds(dtype == MLPK_BF16 ? token_mlp_rr_kernel<bf16_t> : token_mlp_rr_kernel<f16_t>, dim3(grid2), dim3(512), T2_LDS, s, a);
     }
     const int tiles = (M + TM_BM - 1) / TM_BM;
     const unsigned grid = (unsigned)(tiles < tm_grid_cap() ? tiles : tm_grid_cap());
-    hipError_t e;
-    if (dtype == MLPK_BF16) {
-        auto k = token_mlp_kernel<bf16_t>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), TM_LDS, s, a);
-    } else {
-        auto k = token_mlp_kernel<f16_t>;
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, TM_LDS);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), TM_LDS, s, a);
-    }
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(dtype == MLPK_BF16 ? token_mlp_kernel<bf16_t> : token_mlp_kernel<f16_t>, dim3(grid), dim3(512), TM_LDS, s, a);
 }
 
 // The token-mixing PreNormResidual of MLP-Mixer in ONE kernel (mlp_mixer.py:34 with :6-13, :16-27): the LayerNorm + per-image transpose
@@ -1494,52 +1468,31 @@ extern "C" int mlpk_token_mlp_ln(int dtype, void* x, int ldx, int M, int S, cons
     return t4_launch(c, reinterpret_cast<hipStream_t>(stream));
 }
 
+typedef void (*TokenGemmKernel)(const TokenGemmArgs);
+// the instance for a residual mode and an operand loader (lnl: 0 plain, 1 LayerNorm, 2 its residual-add-only form); pipe: the
+// two-iterations-deep pipeline, which exists for the loader variants
+template <typename TT> static TokenGemmKernel token_gemm_instance(bool pipe, int res_mode, int lnl) {
+    const int r = res_mode == MLPK_RES_ADD ? 0 : res_mode == MLPK_RES_MUL ? 1 : 2;
+    if (pipe) {
+        static const TokenGemmKernel k[3] = {token_gemm_pipe_kernel<TT, MLPK_RES_ADD, 1>, token_gemm_pipe_kernel<TT, MLPK_RES_MUL, 1>,
+                                             token_gemm_pipe_kernel<TT, MLPK_RES_NONE, 1>};
+        return lnl == 2 ? token_gemm_pipe_kernel<TT, MLPK_RES_ADD, 2> : k[r];
+    }
+    static const TokenGemmKernel k[2][3] = {
+        {token_gemm_kernel<TT, MLPK_RES_ADD, 0>, token_gemm_kernel<TT, MLPK_RES_MUL, 0>, token_gemm_kernel<TT, MLPK_RES_NONE, 0>},
+        {token_gemm_kernel<TT, MLPK_RES_ADD, 1>, token_gemm_kernel<TT, MLPK_RES_MUL, 1>, token_gemm_kernel<TT, MLPK_RES_NONE, 1>}};
+    return lnl == 2 ? token_gemm_kernel<TT, MLPK_RES_ADD, 2> : k[lnl ? 1 : 0][r];
+}
+
 static int token_gemm_launch(int dtype, TokenGemmArgs& a, int res_mode, int lnl, hipStream_t s) {
     const int tiles = (a.M + T3_BM - 1) / T3_BM;
     const unsigned grid = (unsigned)(tiles < tm_grid_cap() ? tiles : tm_grid_cap());
-#define TG_LAUNCH(TT, RR, LL)                                                                                          \
-    {                                                                                                                   \
-        auto k = token_gemm_kernel<TT, RR, LL>;                                                                         \
-        const int lds = LL ? T3_LDS_LN : T3_LDS;                                                                        \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-        if (e != hipSuccess) return (int)e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, s, a);                                                        \
-    }
-#define TG_RES(TT, LL)                                                                                                 \
-    if (res_mode == MLPK_RES_ADD) TG_LAUNCH(TT, MLPK_RES_ADD, LL) else if (res_mode == MLPK_RES_MUL) TG_LAUNCH(TT, MLPK_RES_MUL, LL) else TG_LAUNCH(TT, MLPK_RES_NONE, LL)
     // round 5: the operand-loader variants with >= 3 groups run as the two-iterations-deep pipeline
     const bool pipe_ok = lnl && a.G >= 3 && a.S % 2 == 0 && a.t_rows <= T5_TMAX && (!a.rscale || (a.rperiod % 8 == 0 && a.rperiod <= T5_TMAX)) &&
-                         !(((uintptr_t)a.ln_mean | (uintptr_t)a.ln_rstd) & 7);
+                         !(((uintptr_t)a.ln_mean | (uintptr_t)a.ln_rstd) & 7);      // (the statistics of a token pair are one 8-byte load)
     if (a.post_scale && !(pipe_ok && a.t_rows <= T5_TMAX / 2)) return MLPK_ESHAPE;   // (the caller applies the Aff itself)
-    if (pipe_ok) {      // (the statistics of a token pair are one 8-byte load)
-#define TP_LAUNCH(TT, RR, LL)                                                                                          \
-    {                                                                                                                   \
-        auto k = token_gemm_pipe_kernel<TT, RR, LL>;                                                                    \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, T5_LDS); \
-        if (e != hipSuccess) return (int)e;                                                                             \
-        hipLaunchKernelGGL(k, dim3(grid), dim3(512), T5_LDS, s, a);                                                     \
-    }
-#define TP_RES(TT)                                                                                                     \
-    if (res_mode == MLPK_RES_ADD) TP_LAUNCH(TT, MLPK_RES_ADD, 1) else if (res_mode == MLPK_RES_MUL) TP_LAUNCH(TT, MLPK_RES_MUL, 1) else TP_LAUNCH(TT, MLPK_RES_NONE, 1)
-        if (dtype == MLPK_BF16) {
-            if (lnl == 2) TP_LAUNCH(bf16_t, MLPK_RES_ADD, 2) else { TP_RES(bf16_t) }
-        } else {
-            if (lnl == 2) TP_LAUNCH(f16_t, MLPK_RES_ADD, 2) else { TP_RES(f16_t) }
-        }
-#undef TP_RES
-#undef TP_LAUNCH
-        MLPK_LAUNCH_CHECK();
-        return 0;
-    }
-    if (dtype == MLPK_BF16) {
-        if (lnl == 2) TG_LAUNCH(bf16_t, MLPK_RES_ADD, 2) else if (lnl) { TG_RES(bf16_t, 1) } else { TG_RES(bf16_t, 0) }
-    } else {
-        if (lnl == 2) TG_LAUNCH(f16_t, MLPK_RES_ADD, 2) else if (lnl) { TG_RES(f16_t, 1) } else { TG_RES(f16_t, 0) }
-    }
-#undef TG_RES
-#undef TG_LAUNCH
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    const TokenGemmKernel k = dtype == MLPK_BF16 ? token_gemm_instance<bf16_t>(pipe_ok, res_mode, lnl) : token_gemm_instance<f16_t>(pipe_ok, res_mode, lnl);
+    return launch_lds(k, dim3(grid), dim3(512), pipe_ok ? T5_LDS : lnl ? T3_LDS_LN : T3_LDS, s, a);
 }
 
 extern "C" int mlpk_token_gemm(int dtype, const void* xt, int ldxt, int M, int S, const void* w, int ldw, const float* bias, int ngroups,

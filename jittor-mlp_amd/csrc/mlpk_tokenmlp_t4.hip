@@ -82,13 +82,7 @@ int t4_launch(const T4Call& c, hipStream_t stream) {
     a.nit = c.G + 2 + a.lead;
     a.S = c.S;
     a.ln_mean = c.ln_mean; a.ln_rstd = c.ln_rstd; a.gamma = c.gamma; a.beta = c.beta;
-    hipError_t e = hipFuncSetAttribute(v->fn, hipFuncAttributeMaxDynamicSharedMemorySize, T4_LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    void* params[] = {&a};
-    e = hipLaunchKernel(v->fn, dim3(a.grid), dim3(256), params, T4_LDS_BYTES, stream);
-    if (e != hipSuccess) return (int)e;
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(v->fn, dim3(a.grid), dim3(256), T4_LDS_BYTES, stream, &a);
 }
 
 }  // namespace mlpk

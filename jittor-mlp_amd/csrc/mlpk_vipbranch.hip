@@ -291,12 +291,7 @@ static int vip_branch_launch(VipBranchArgs a, hipStream_t s) {
     const int lds = 2 * sg * SLAB + fixed;
     const int tiles = (a.nslabs + sg - 1) / sg;
     const int grid = tiles < vb_grid_cap() ? tiles : vb_grid_cap();
-    auto k = vip_branch_kernel<T, NKS, NCW>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), lds, s, a);
-    MLPK_LAUNCH_CHECK();
-    return 0;
+    return launch_lds(vip_branch_kernel<T, NKS, NCW>, dim3((unsigned)grid), dim3(256), lds, s, a);
 }
 
 }  // namespace mlpk

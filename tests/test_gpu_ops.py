@@ -778,6 +778,44 @@ def test_gemm_two_tile_heights_in_one_launch():
     assert (outs[("1", False)][0][:64].double() - ref).abs().max().item() < EPS[dtype] * 4 * max(1.0, ref.abs().max().item())
 
 
+def test_gemm_pair_kernel_every_short_height():
+    """The three instances of gemm_nt_p8_pair_kernel -- 256-row tiles followed by tiles of 64, 128 or 192 rows -- at a few hundred rows: with
+    plan bit 16 (whole tiles + one short panel) M = 320 / 384 / 448 plan 256 + 64 / 128 / 192.  bias + residual, with and without the
+    by-product statistics: the dispatch names the pair kernel, one launch per height (MLPK_P8_PAIR=0) gives the same bits in C and in
+    the statistics planes, and C is the fp64 restatement's within the gate of test_gemm_two_tile_heights_in_one_launch."""
+    import ctypes
+    pkg = load_pkg()
+    E, N = pkg.engine, pkg._native
+    Nn, K, dtype = 256, 128, torch.bfloat16
+    for M in (320, 384, 448):
+        A, B = rnd((M, K), dtype, 1).to(dev()), rnd((Nn, K), dtype, 2, 1.0 / math.sqrt(K)).to(dev())
+        R, bias = rnd((M, Nn), dtype, 3).to(dev()), rnd((Nn,), torch.float32, 4).to(dev())
+        ref = A.cpu().double() @ B.cpu().double().t() + bias.cpu().double() + R.cpu().double()
+        outs = {}
+        for pair in ("1", "0"):
+            os.environ["MLPK_P8_PAIR"] = pair
+            try:
+                for stats in (False, True):
+                    C = torch.zeros((M, Nn), dtype=dtype, device=dev())
+                    ws = E.Workspace(dev(), dtype) if stats else None
+                    d, part = E.gemm(A, B, C, M, Nn, K, bias=bias, R=R, res=N.RES_ADD, algo=14, dbg=16, part=(ws, "p") if stats else None, _defer=True)
+                    assert (part is not None) == stats
+                    name = ctypes.create_string_buffer(96)
+                    assert N.lib().mlpk_gemm_kernel_name(ctypes.byref(d), name, 96) == 0
+                    assert name.value.decode() == "gemm_nt_p8%s_kernel<EPI=%d> rows 256+%d" % ("_pair" if pair == "1" else "", 2 if stats else 1, M - 256)
+                    N.check(N.lib().mlpk_gemm_nt(ctypes.byref(d), E.stream()), "mlpk_gemm_nt")
+                    torch.cuda.synchronize()
+                    outs[(pair, stats)] = (C, part[0].clone() if stats else None)
+            finally:
+                del os.environ["MLPK_P8_PAIR"]
+        for stats in (False, True):
+            assert torch.equal(outs[("1", stats)][0], outs[("0", stats)][0])
+        assert torch.equal(outs[("1", True)][0], outs[("1", False)][0])
+        assert torch.isfinite(outs[("1", True)][1]).all() and torch.equal(outs[("1", True)][1], outs[("0", True)][1])
+        err = (outs[("1", False)][0].cpu().double() - ref).abs().max().item()
+        assert err < EPS[dtype] * 4 * max(1.0, ref.abs().max().item()), (M, err)
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_fused_token_mlp_generated_kernel(dtype):
     """layout 2 of mlpk_token_mlp (the generated one-wave-per-SIMD kernel, csrc/gen/t4gen.py): against the fp64 restatement of

@@ -157,7 +157,7 @@ def rd(shape, dtype, seed, scale=1.0):
 
 # ------------------------------------------------------------------ mlpk_gemm_nt
 def vec_class(ld, lead, es):
-    """gemm_prepare's store / residual-load class of an operand at element offset `lead` of an allocator-aligned buffer: 0 scalar, 1 = 4-element
+    """gemm_resolve's store / residual-load class of an operand at element offset `lead` of an allocator-aligned buffer: 0 scalar, 1 = 4-element
     vectors, 2 = 16-byte vectors"""
     c = int(ld % 4 == 0 and (lead * es) % (4 * es) == 0)
     if c and ld % 8 == 0 and (lead * es) % 16 == 0:
