@@ -105,6 +105,11 @@ const char* mlpk_strerror(int code);
  * v = v * rscale[m % rperiod]           (rscale may be NULL)
  * v = v + R[...]  (res_mode ADD)  |  v = v * R[...]  (res_mode MUL)
  * C[...] = (dtype) v
+ * Roundings to the storage type.  fp32 accumulation throughout; without a residual v is rounded ONCE, where it is stored.  With a
+ * residual / gate and a 16-bit dtype v is rounded TWICE: the 16-bit epilogues (every tile's row-major store, the persistent and the
+ * generated tile, and the token-transposed store of a tile that lies inside one image) finish v, round it to the storage type, and
+ * then compute (dtype)((float)(dtype)v (+|*) R) on 16-byte chunks.  Only the token-transposed store of a tile that straddles images
+ * applies R to the fp32 value (one rounding).  tests/test_gpu_rounding.py holds every path to these counts.
  * Addressing of C (and R with ldr):
  *   out_mode ROWMAJOR : C[m*ldc + n]
  *   out_mode TOKEN_T  : rows are (image b, channel c) pairs, m = b*t_rows + c, and columns are
