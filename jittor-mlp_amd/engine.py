@@ -153,10 +153,30 @@ def pack_ln_folded(w, b, gamma, beta, dtype, device, kpad=8):
 
 
 def f32(v, device):
-    """Per-channel vectors always travel as float32."""
+    """Per-channel vectors always travel as float32.  Always a copy: for an fp32 parameter already on the device the conversions are
+    views, and a pack that aliased its parameter would change under a forward still queued on another stream when the parameter is
+    updated in place (load_state_dict, an optimizer step) -- a forward reads packs only (streams)."""
     if v is None:
         return None
-    return v.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+    out = v.detach().to(device=device, dtype=torch.float32).reshape(-1).contiguous()
+    return out.clone() if out.data_ptr() == v.data_ptr() else out
+
+
+def pack_tensors(pack):
+    """Every device tensor of what a `_pack` returned, whatever the nesting (dicts, tuples and lists of tensors, ints and None; a
+    nested module's pack handed through): one per storage."""
+    out, seen, stack = [], set(), [pack]
+    while stack:
+        v = stack.pop()
+        if torch.is_tensor(v):
+            if v.is_cuda and v.untyped_storage().data_ptr() not in seen:
+                seen.add(v.untyped_storage().data_ptr())
+                out.append(v)
+        elif isinstance(v, dict):
+            stack.extend(v.values())
+        elif isinstance(v, (tuple, list)):
+            stack.extend(v)
+    return out
 
 
 # ------------------------------------------------------------------ kernel wrappers
@@ -451,9 +471,9 @@ def pack_token_mlp(w1, b1, w2, b2, dtype, device, sp, layout=None, t_rows=None):
     if layout in (2, 3):
         # include/mlpk.h: W2 group-major -- (nch + 1) groups x 224 token rows x 32 k slots, slot 16 kk + 8 h + e of a group <- hidden
         # 16 kk + 8 (e >> 2) + 4 h + (e & 3); group nch and the token rows behind S are zeros; b1 / b2 as padded tables
-        slot = torch.arange(32)
+        slot = torch.arange(32, device=device)        # (built on the device: a table copied up from the host would make the packing wait for its stream)
         kk, hh, e = slot // 16, (slot // 8) % 2, slot % 8
-        src = (16 * kk + 8 * (e // 4) + 4 * hh + (e % 4)).to(device)
+        src = 16 * kk + 8 * (e // 4) + 4 * hh + (e % 4)
         # layout 3 (bf16 storage): the kernel keeps the hidden in f16 and multiplies it by f16 weights -- W2 rounded from fp32 to f16 HERE
         w2dt = torch.float16 if layout == 3 else dtype
         if layout == 3:
@@ -469,9 +489,9 @@ def pack_token_mlp(w1, b1, w2, b2, dtype, device, sp, layout=None, t_rows=None):
         return w1p, b1t, w2g.view((nch + 1) * 224, 32), b2t, nch, layout
     if layout == 1:
         # column slot 8 f + e of every 32-column group <- column (e < 4 ? 4 f + e : 16 + 4 f + e - 4)   (include/mlpk.h)
-        slot = torch.arange(32)
+        slot = torch.arange(32, device=device)
         f, e = slot // 8, slot % 8
-        src = torch.where(e < 4, 4 * f + e, 16 + 4 * f + e - 4).to(device)
+        src = torch.where(e < 4, 4 * f + e, 16 + 4 * f + e - 4)
         w2p = w2p.view(S, nch, 32)[:, :, src].reshape(S, nch * ch).contiguous()
     return w1p, b1p, w2p, f32(b2, device), nch, layout
 
@@ -536,13 +556,13 @@ def pack_channel_mlp_fused(w1, b1, w2, b2, dtype, device, gamma=None, beta=None,
         b2v = b2v * cs
     w2p = torch.zeros((C, nch * 32), dtype=dtype, device=device)
     w2p[:, :T] = w2.to(dtype)
-    slot = torch.arange(32)
+    slot = torch.arange(32, device=device)
     f, e = slot // 8, slot % 8
-    col = torch.where(e < 4, 4 * f + e, 16 + 4 * f + e - 4).to(device)          # hidden unit at k slot 8 f + e
+    col = torch.where(e < 4, 4 * f + e, 16 + 4 * f + e - 4)         # hidden unit at k slot 8 f + e
     h, f4, r = slot // 16, (slot // 4) % 4, slot % 4
-    row = (8 * f4 + 4 * h + r).to(device)                                        # output channel at row 16 h + 4 f + r
+    row = 8 * f4 + 4 * h + r                                     # output channel at row 16 h + 4 f + r
     w2p = w2p.view(C // 32, 32, nch, 32)[:, row][:, :, :, col].reshape(C, nch * 32).contiguous()
-    return w1p, b1p, csum, w2p, b2v.contiguous(), nch
+    return w1p, b1p, csum, w2p, f32(b2v, device), nch          # (f32: never an alias of fc2's bias)
 
 
 def channel_mlp_fused(x, rows, C, pack, out, *, R=None, ln=None, ln_group=1, part=None):
@@ -920,13 +940,32 @@ class EngineModule(torch.nn.Module):
         return state
 
     def _get_pack(self, dtype, device):
-        key = (dtype, str(device))
+        # `_packs` maps (dtype, device) to the entry (stamp, pack, event behind the packing, the pack's tensors) and, for every stream
+        # that may read the pack, (dtype, device, stream) to the same entry.  The packing kernels are asynchronous on the stream of the
+        # call that missed; a call on any other stream (parallel.InFlight, a caller's own streams, a side stream) is ordered behind them
+        # by a stream wait on the event, and the tensors are made known to the caching allocator for that stream (record_stream), so
+        # that a replaced or invalidated pack is not handed out again while a forward queued there still reads it.  Both happen once
+        # per (pack, stream); a later hit is the one lookup below and never touches the host side of a stream.
+        sdev, cur = str(device), stream()
         stamp = self._param_stamp()
-        hit = self._packs.get(key)
+        hit = self._packs.get((dtype, sdev, cur))
+        if hit is not None and hit[0] == stamp:
+            return hit[1]
+        hit = self._packs.get((dtype, sdev))
         if hit is None or hit[0] != stamp:
+            for k in [k for k, v in self._packs.items() if v is hit]:          # the replaced pack goes with every key that led to it
+                del self._packs[k]
             with torch.no_grad():
-                hit = (stamp, self._pack(dtype, device))
-            self._packs[key] = hit
+                pack = self._pack(dtype, device)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream())
+            hit = self._packs[(dtype, sdev)] = (stamp, pack, ev, pack_tensors(pack))
+        else:
+            here = torch.cuda.current_stream()
+            here.wait_event(hit[2])
+            for t in hit[3]:
+                t.record_stream(here)
+        self._packs[(dtype, sdev, cur)] = hit
         return hit[1]
 
     def _get_space(self, batch, dtype, device):

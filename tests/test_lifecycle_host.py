@@ -259,6 +259,41 @@ def test_data_inplace_writes_are_invisible_to_the_stamp(name):
     assert m._param_stamp() == before
 
 
+def _span(t):
+    s = t.untyped_storage()
+    return s.data_ptr(), s.data_ptr() + s.nbytes()
+
+
+@pytest.mark.parametrize("name,dtype", [(n, d) for n in HOST for d in ("fp32", "bf16")] + [(n, "bf16") for n in FUSED])
+def test_no_eval_pack_tensor_aliases_a_parameter(pkg, name, dtype):
+    """a forward reads packed weights only (streams): an in-place parameter update must not reach a forward that
+    is still queued on another stream, so no tensor of `_pack`'s result may share storage with a parameter or buffer -- fp32 is the
+    likely miss, where `.to(float32)` / `.reshape` / `.contiguous()` of a parameter are views.  Packed on the CPU: the packing is plain
+    torch, and the aliasing does not depend on the device.  engine.pack_tensors (what _get_pack hands to record_stream) is held to the
+    same walk: every leaf is a tensor, a plain number or None."""
+    E = pkg.engine
+    m = config(name).fresh()
+    with torch.no_grad():
+        pk = m._pack({"fp32": torch.float32, "bf16": torch.bfloat16}[dtype], torch.device("cpu"))
+    leaves, stack = [], [pk]
+    while stack:
+        v = stack.pop()
+        if isinstance(v, dict):
+            stack.extend(v.values())
+        elif isinstance(v, (tuple, list)):
+            stack.extend(v)
+        else:
+            assert v is None or torch.is_tensor(v) or isinstance(v, (int, float, bool, str)), (name, type(v).__name__, "engine.pack_tensors does not walk this")
+            if torch.is_tensor(v):
+                leaves.append(v)
+    assert len(leaves) >= 4
+    own = {k: _span(t) for k, t in m.state_dict(keep_vars=True).items()}
+    for t in leaves:
+        lo, hi = _span(t)
+        shared = [k for k, (a, b) in own.items() if not (b <= lo or hi <= a)]
+        assert not shared, (name, dtype, tuple(t.shape), "a pack tensor aliases", shared)
+
+
 def _fill_caches(pkg, m, marker):
     """what a forward leaves behind, without a launch: an entry in _packs and _spaces of every EngineModule of the tree"""
     E = pkg.engine
