@@ -58,6 +58,9 @@
  *   mlpk_vip_branch     LayerNorm + rearrange + Linear of ViP's h / w branch in ONE kernel, the rearrange as LDS staging order (vip.py:66-76)
  *   mlpk_s2_shift       Spatial_Shift (s2_mlp_v1.py:19-25), out of place
  *   mlpk_wave_patm      WaveMLP's PATM phase modulation + both grouped 7-tap convolutions (wave_mlp.py:46-60) in one pass
+ *   mlpk_raft_gather_ln, mlpk_raft_scatter_add   RaftMLP's raft token mixing (raft_mlp.py:114-146,333-362): LayerNorm + the re-layout into the
+ *                       token MLP's operand rows, and the residual addition of its result back onto the map; the MLP itself is
+ *                       mlpk_channel_mlp or two mlpk_gemm_nt
  *   mlpk_dwconv_nhwc    depthwise Conv2d(k, groups=dim, padding="same") + GELU + BatchNorm(eval) + residual:
  *                       conv_mixer.py:5-11,24-28
  */
@@ -740,6 +743,27 @@ int mlpk_dropout(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, in
 int mlpk_wave_patm_supported(int dtype, int B, int H, int W, int C);
 int mlpk_wave_patm(int dtype, const void* y, int64_t ldy, const float* wh, const float* ww, void* out_h, void* out_w, int64_t ldo, int B, int H, int W,
                    int C, void* stream);
+
+/* RaftMLP's raft token mixing (PermutedBlock, raft_mlp.py:114-146 inside SerialPermutedLevel :333-362; SpatiallySeparatedTokenBlock :95-111 is r = 1).
+ * x: channel-last rows of the (B, H, W) map at row pitch x_pitch >= C.  r = raft_size, Co = C / r, channel c = j Co + co (j < r).  axis 0 (vertical):
+ * L = H, q runs over w, pix(l, q) = (b H + l) W + q; axis 1 (horizontal): L = W, q runs over h, pix(l, q) = (b H + q) W + l.  Q = the extent of q,
+ * D = r L.  Row (b, q, co) of the token MLP's operand is the vector z[j L + l] over the r channel groups and the L positions of one line:
+ *   gather_ln  : a[((b Q + q) Co + co) a_pitch + j L + l] = (x[pix(l, q), j Co + co] - mean[pix]) rstd[pix] gamma[j Co + co] + beta[j Co + co]
+ *                in fp32 with one rounding to the storage type: mlpk_norm_apply's expression.  mean / rstd per pixel (B H W), both NULL: 0 / 1; gamma /
+ *                beta per channel, indexed by the ACTIVATION's channel (the reference stores its LayerNorm affine in (co, j) order: the packer
+ *                permutes it), NULL: 1 / 0.  Columns [D, kp) of every row are written as zeros (kp = the K the product will be given), columns
+ *                [kp, a_pitch) are not touched.
+ *   scatter_add: x[pix(l, q), j Co + co] = round(float(x[..]) + float(y[((b Q + q) Co + co) y_pitch + j L + l])), one rounding: the residual addition on
+ *                the un-normalised x.  Columns of y at or beyond D are never read, columns of x at or beyond C never touched.
+ * Both return before anything touches a device: a missing pointer (or only one of mean / rstd) MLPK_ENULL; a dtype other than fp32 / fp16 / bf16
+ * MLPK_EDTYPE; a non-positive extent, C % r != 0, axis not 0 / 1, kp < D, kp > a_pitch, y_pitch < D, x_pitch < C, C not a whole number of 16-byte
+ * vectors (C % 8 for 16-bit, C % 4 for fp32), or a line of L pixels x C channels that does not fit the 160 KiB of LDS it is turned over in
+ * (C (ceil(L / e) | 1) 4 bytes, e = pixels per dword) MLPK_ESHAPE; a base pointer or pitch off a 16-byte boundary MLPK_EALIGN.
+ * mlpk_raft_supported: 1 exactly where both entries accept the dtype and shape, else 0.  The results do not depend on the pitches. */
+int mlpk_raft_supported(int dtype, int H, int W, int C, int r, int axis);
+int mlpk_raft_gather_ln(int dtype, const void* x, int64_t x_pitch, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                        void* a, int64_t a_pitch, int kp, int B, int H, int W, int C, int r, int axis, void* stream);
+int mlpk_raft_scatter_add(int dtype, void* x, int64_t x_pitch, const void* y, int64_t y_pitch, int B, int H, int W, int C, int r, int axis, void* stream);
 
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that

@@ -151,6 +151,11 @@ PROTOTYPES = {
     "mlpk_wave_patm_supported": (c_int, [c_int] * 5),
     # (dtype, y, ldy, wh, ww, out_h, out_w, ldo, B, H, W, C, stream)
     "mlpk_wave_patm": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_i64] + [c_int] * 4 + [c_void_p]),
+    "mlpk_raft_supported": (c_int, [c_int] * 6),
+    # (dtype, x, x_pitch, mean, rstd, gamma, beta, a, a_pitch, kp, B, H, W, C, r, axis, stream)
+    "mlpk_raft_gather_ln": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64] + [c_int] * 7 + [c_void_p]),
+    # (dtype, x, x_pitch, y, y_pitch, B, H, W, C, r, axis, stream)
+    "mlpk_raft_scatter_add": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_i64] + [c_int] * 6 + [c_void_p]),
 }
 
 _lib = None

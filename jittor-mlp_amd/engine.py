@@ -730,6 +730,23 @@ def wave_patm(y, wh, ww, out_h, out_w, B, H, W, C):
                                    stream()), "mlpk_wave_patm")
 
 
+def raft_supported(dtype, H, W, C, r, axis):
+    return bool(N.lib().mlpk_raft_supported(dtype_code(dtype), H, W, C, r, axis))
+
+
+def raft_gather_ln(x, mean, rstd, gamma, beta, a, kp, B, H, W, C, r, axis):
+    """RaftMLP's raft token mixing, first half (mlpk_raft_gather_ln): the LayerNorm of the channel-last rows x and their re-layout into the token
+    MLP's operand rows a[(b, q, co), j * L + l], zeros in columns [r * L, kp)"""
+    N.check(N.lib().mlpk_raft_gather_ln(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(a), a.stride(0), kp,
+                                        B, H, W, C, r, axis, stream()), "mlpk_raft_gather_ln")
+
+
+def raft_scatter_add(x, y, B, H, W, C, r, axis):
+    """... second half (mlpk_raft_scatter_add): x += the token MLP's output rows y, laid back onto the map"""
+    N.check(N.lib().mlpk_raft_scatter_add(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(y), y.stride(0), B, H, W, C, r, axis, stream()),
+            "mlpk_raft_scatter_add")
+
+
 def split_softmax(hat, bar, B, C):
     N.check(N.lib().mlpk_split_softmax(ptr(hat), ptr(bar), B, C, stream()), "mlpk_split_softmax")
 
