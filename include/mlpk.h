@@ -765,6 +765,36 @@ int mlpk_raft_gather_ln(int dtype, const void* x, int64_t x_pitch, const float* 
                         void* a, int64_t a_pitch, int kp, int B, int H, int W, int C, int r, int axis, void* stream);
 int mlpk_raft_scatter_add(int dtype, void* x, int64_t x_pitch, const void* y, int64_t y_pitch, int B, int H, int W, int C, int r, int axis, void* stream);
 
+/* ActiveMLP's active token mixer (ATMLayer, active_mlp.py:108-127; ATMOp :65-81): the sampling in front of its three products, in one pass.
+ * x: channel-last rows of the (B, H, W) map at row pitch x_pitch >= C; the operand is v[pix, c] = round_to_storage((x[pix, c] - mean[pix]) rstd[pix]
+ * gamma[c] + beta[c]), the expression and rounding of mlpk_norm_apply, never stored on its own.  mean / rstd per pixel (B H W), both NULL: 0 / 1;
+ * gamma / beta per channel, NULL: 1 / 0.  off: rows (B H W, 2C / share) of the storage type at row pitch off_pitch -- the offset Linear's output
+ * as it lies, NOT repeated: `share` adjacent channels use one column (share = 1: one offset per channel).  ATMOp puts its offset into
+ * deform_conv2d's dx slots (branch w) or dy slots (branch h) and zero into the others, and bilinear sampling with one offset identically zero
+ * is linear interpolation along one axis.  With p = position + float(offset) on an axis of L pixels the sample is 0 unless -1 < p < L; else, with
+ * i0 = floor(p) and f = p - i0, it is (1 - f) v[i0] + f v[i0 + 1], each term dropped when its index is outside [0, L - 1] (continuous in p):
+ *   out_w[b,y,x,c] = the sample of v[b, y, ., c] at p = x + off[pix, c / share],       L = W
+ *   out_h[b,y,x,c] = the sample of v[b, ., x, c] at p = y + off[pix, (C + c) / share], L = H
+ *   out_c          = v
+ * Any of the three outputs may be NULL (not all); they share the row pitch out_pitch >= C and may be column slices of one buffer; columns at or
+ * beyond C of an output row are not touched.  Position, weights and sum in fp32, one rounding at the store; a tap whose weight is exactly 0 is
+ * not added, so an integer offset returns v's bits.  NaN, +-inf and arbitrarily large offsets give +0: "inside" is decided by float
+ * comparisons before any conversion to an integer, and no address is formed from an index that has not been range-checked (csrc/mlpk_atm_tap.h,
+ * one source expression for the kernel and for mlpk_atm_tap).
+ * Returns before anything touches a device: a missing x / off, all three outputs NULL, or only one of mean / rstd MLPK_ENULL; a dtype other than
+ * fp32 / fp16 / bf16 MLPK_EDTYPE; a non-positive extent, share <= 0, 2C % share != 0, C not a whole number of 16-byte vectors (C % 8 for 16-bit,
+ * C % 4 for fp32), x_pitch < C, out_pitch < C, off_pitch < 2C / share, or max(H, W) > 4096 (a line of one channel vector is staged in 64 KiB of
+ * LDS) MLPK_ESHAPE; x, an output, x_pitch or out_pitch off a 16-byte boundary, or off not aligned to its element, MLPK_EALIGN.
+ * mlpk_atm_sample_supported: 1 exactly where the entry accepts the dtype and shape, else 0.  The results do not depend on the pitches.
+ * mlpk_atm_tap: the tap function itself on the host -- position pos in [0, L) -- writes i0, i1, w0 = 1 - f, w1 = f and returns bit 0 = the first
+ * tap contributes, bit 1 = the second (an index is inside [0, L - 1] whenever its bit is set, 0 otherwise); NULL pointer MLPK_ENULL, L <= 0 or pos
+ * outside [0, L) MLPK_ESHAPE. */
+int mlpk_atm_sample_supported(int dtype, int H, int W, int C, int share);
+int mlpk_atm_sample(int dtype, const void* x, int64_t x_pitch, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                    const void* off, int64_t off_pitch, int share, void* out_w, void* out_h, void* out_c, int64_t out_pitch, int B, int H, int W,
+                    int C, void* stream);
+int mlpk_atm_tap(float off, int pos, int L, int* i0, int* i1, float* w0, float* w1);
+
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that
  * product) -- the better plan when several forwards share the chip (parallel.InFlight) and the other request fills the last round anyway.  Same K order per output

@@ -156,6 +156,11 @@ PROTOTYPES = {
     "mlpk_raft_gather_ln": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64] + [c_int] * 7 + [c_void_p]),
     # (dtype, x, x_pitch, y, y_pitch, B, H, W, C, r, axis, stream)
     "mlpk_raft_scatter_add": (c_int, [c_int, c_void_p, c_i64, c_void_p, c_i64] + [c_int] * 6 + [c_void_p]),
+    "mlpk_atm_sample_supported": (c_int, [c_int] * 5),
+    # (dtype, x, x_pitch, mean, rstd, gamma, beta, off, off_pitch, share, out_w, out_h, out_c, out_pitch, B, H, W, C, stream)
+    "mlpk_atm_sample": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_int] + [c_void_p] * 3 + [c_i64] + [c_int] * 4 + [c_void_p]),
+    # (off, pos, L, i0, i1, w0, w1)
+    "mlpk_atm_tap": (c_int, [ctypes.c_float, c_int, c_int] + [c_void_p] * 4),
 }
 
 _lib = None

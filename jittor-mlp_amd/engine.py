@@ -747,6 +747,23 @@ def raft_scatter_add(x, y, B, H, W, C, r, axis):
             "mlpk_raft_scatter_add")
 
 
+def atm_sample_supported(dtype, H, W, C, share):
+    return bool(N.lib().mlpk_atm_sample_supported(dtype_code(dtype), H, W, C, share))
+
+
+def atm_sample(x, mean, rstd, gamma, beta, off, share, out_w, out_h, out_c, B, H, W, C):
+    """ActiveMLP's active token mixer (mlpk_atm_sample): LayerNorm(x) sampled along w and along h at the per-pixel, per-channel-group offsets
+    `off` (rows of 2C / share columns), and LayerNorm(x) itself, in one pass.  Any output may be None (not all); they share one row stride."""
+    ref = next(o for o in (out_w, out_h, out_c) if o is not None)
+    N.check(N.lib().mlpk_atm_sample(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(off), off.stride(0), share,
+                                    ptr(out_w), ptr(out_h), ptr(out_c), ref.stride(0), B, H, W, C, stream()), "mlpk_atm_sample")
+
+
+def dwconv_plain_nhwc(x, out, B, H, W, C, k, w, bias):
+    """depthwise Conv2d(k, groups = C, padding = "same") on dense channel-last rows, no epilogue (mlpk_dwconv_plain_nhwc): w fp32 [k * k][C]"""
+    N.check(N.lib().mlpk_dwconv_plain_nhwc(dtype_code(x.dtype), 0, ptr(x), ptr(out), B, H, W, C, k, ptr(w), ptr(bias), stream()), "mlpk_dwconv_plain_nhwc")
+
+
 def split_softmax(hat, bar, B, C):
     N.check(N.lib().mlpk_split_softmax(ptr(hat), ptr(bar), B, C, stream()), "mlpk_split_softmax")
 

@@ -17,6 +17,7 @@ from .swin_mlp import SwinMLP  # noqa: F401  
 from .cycle_mlp import CycleNet, CycleMLP_B1, CycleMLP_B2, CycleMLP_B3, CycleMLP_B4, CycleMLP_B5  # noqa: F401  
 from .wave_mlp import WaveMLP  # noqa: F401
 from .raft_mlp import RaftMLP  # noqa: F401
+from .active_mlp import ActiveMLP, ActiveSmall, ActiveBase, ActiveLarge  # noqa: F401
 from .utils import Shift  # noqa: F401
 # secondary classes the reference lets users import from the sub-modules
 from .mlp_mixer import MLPMixer  # noqa: F401
@@ -28,4 +29,5 @@ from .cycle_mlp import CycleFC, CycleMLP, CycleBlock  # noqa: F401
 
 __all__ = ["gMLPForImageClassification", "ResMLPForImageClassification", "MLPMixerForImageClassification", "ViP",
            "S2MLPv1", "S2MLPv1_deep", "S2MLPv1_wide", "S2MLPv2", "ConvMixer", "AS_MLP", "SparseMLP", "HireMLP", "MS_MLP", "SwinMLP", "CycleNet",
-           "CycleMLP_B1", "CycleMLP_B2", "CycleMLP_B3", "CycleMLP_B4", "CycleMLP_B5", "WaveMLP", "RaftMLP", "Shift"]
+           "CycleMLP_B1", "CycleMLP_B2", "CycleMLP_B3", "CycleMLP_B4", "CycleMLP_B5", "WaveMLP", "RaftMLP", "ActiveMLP",
+           "ActiveSmall", "ActiveBase", "ActiveLarge", "Shift"]
