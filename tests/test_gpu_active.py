@@ -393,37 +393,6 @@ def test_deterministic_and_in_flight(meta):
     assert len({id(s) for _, s in pending}) == 2
 
 
-class WithOffset(torch.nn.Module):
-    """ATMLayer as a one-argument callable for the ownership check: the offsets are a fixed tensor"""
-
-    def __init__(self, layer, offset):
-        super().__init__()
-        self.layer = layer
-        self.offset = offset
-
-    def forward(self, x):
-        return self.layer(x, self.offset.to(x.dtype))
-
-
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
-@pytest.mark.parametrize("what", ["model", "atm_layer"])
-def test_results_and_inputs_are_the_callers(what, dtype, meta):
-    """tests/test_gpu_lifecycle.py's ownership check (`check_callers_own`) on ActiveMLP and on ATMLayer: the result survives later forwards and
-    shares no storage with a workspace, the input is not written, a strided batch slice and a channels_last batch give the bits of their
-    contiguous copies.  (That file's table of EngineModule classes cannot be extended from here.)"""
-    from test_gpu_lifecycle import check_callers_own
-    if what == "model":
-        model, x = tiny_model(meta, "s64")
-        x = torch.cat([x, x.flip(0)[:1]])
-        assert check_callers_own(model, model, x.to(dtype)) >= 1
-        return
-    H, W, C = meta["blocks"]["atm_5_7_16"]
-    blk = load_portable(mp().active_mlp.ATMLayer(C), meta["block_seed"]).to(DEV).eval()
-    off = torch.from_numpy(portable_tensor("offset", (3, 2 * C, H, W), -3.0, 3.0, seed=4)).to(DEV)
-    x = torch.from_numpy(portable_input((3, H, W, C), seed=3)).to(DEV).to(dtype)
-    assert check_callers_own(blk, WithOffset(blk, off), x) >= 1
-
-
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_weight_update_reaches_the_next_forward(dtype, meta):
     """packed weights follow the parameters: an in-place update of an offset Linear's bias, of an atm_w weight and of a PEG tap each changes the

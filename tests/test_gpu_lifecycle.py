@@ -10,7 +10,8 @@ input, batch and dtype, compared with torch.equal.  The cold model is what test_
 the reference; every kernel has a fixed summation order (test_tiny_golden asserts run-to-run equality), so zero difference is the gate and
 no tolerance appears in this file.
 
-Tables (tests/test_lifecycle_host.py): TINY = one tiny_*.npz configuration per family + WaveMLP-T (eval only); FUSED = the twelve benchmark
+Tables (tests/test_lifecycle_host.py): TINY = one tiny_*.npz configuration per family; EVAL_ONLY = the inference-only families on their own
+fixtures' tiny configurations (WaveMLP-T, RaftMLP with either head, ActiveMLP): every update form but the optimizer steps; FUSED = the twelve benchmark
 families at benchmark widths and reduced depth (the kwargs of train_grad_widths.npz, portable weights, 224 x 224): the table that reaches
 the generated token kernel, as_conv2_stats with its counters, the fused channel MLP, swin_spatial_stats, the tiled mix-shift and the
 vip_branch kernels, where the tiny models mostly take the fallback paths."""
@@ -30,7 +31,7 @@ from torch import nn
 
 from conftest import GOLDEN, load_pkg
 from test_gpu_models import build_from_tiny
-from test_lifecycle_host import (AT224, BN_FAMILIES, FUSED, TINY, VISIBLE_UPDATES, WAVE, adamw, config, noise_like, one_per_role, sgd,
+from test_lifecycle_host import (AT224, BN_FAMILIES, EVAL_ONLY, FUSED, TINY, VISIBLE_UPDATES, WAVE, adamw, config, noise_like, one_per_role, sgd,
                                  u_data_inplace_then_invalidate, u_no_grad_add)
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +99,7 @@ def check_updates(name, dtype, batch=2):
     cfg = config(name)
     x = images(cfg, batch, dtype)
     forms = [(u, False) for u in VISIBLE_UPDATES + [u_data_inplace_then_invalidate]]
-    if name != WAVE:
+    if name not in EVAL_ONLY:
         forms += [(u_optimizer_step(sgd), True), (u_optimizer_step(adamw), True)]
     if name in BN_FAMILIES:                        # (under no_grad only ConvMixer's train mode runs on batch statistics; Sparse-MLP's takes the eval path)
         forms += [(u_bn_train_forward(True), True)] + ([(u_bn_train_forward(False), True)] if name.startswith("convmixer") else [])
@@ -128,7 +129,7 @@ def check_updates(name, dtype, batch=2):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", TINY + [WAVE])
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY)
 def test_weight_update_reaches_the_next_forward_tiny(name, dtype):
     """load_state_dict, no_grad add_, `p.data = t`, `mod.weight = nn.Parameter`, .half() / update / .float(), SGD and AdamW steps after a
     train-mode backward, a train-mode forward that moves BatchNorm's running statistics, set_compute_dtype back and forth, and a `.data`
@@ -142,7 +143,7 @@ def test_weight_update_reaches_the_next_forward_fused(name):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", TINY + [WAVE])
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY)
 def test_every_parameter_role_reaches_the_next_forward(name, dtype):
     """one entry per role (the name with its digits stripped; no role skipped) perturbed at a time on ONE long-lived model: the stamp
     moves and warm == cold.  The folded ones are the likely misses: LayerNorm gamma / beta inside the next GEMM's weight, bias and csum,
@@ -201,7 +202,7 @@ def _check_nothing_left_behind(name, dtype):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "fp16", "bf16"])
-@pytest.mark.parametrize("name", TINY + [WAVE])
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY)
 def test_forward_leaves_nothing_behind_tiny(name, dtype):
     """o1 = m(x1); m(x2), m(one all-NaN image), m(1e4 x inputs); m(x1) == o1.  Then batches 2, 1, 3, 5, 4, 2 in one model's life, NaN and
     large inputs in between: each result equals the cold model at that batch."""
@@ -214,7 +215,7 @@ def test_forward_leaves_nothing_behind_fused(name, dtype):
     check_nothing_left_behind(name, DT[dtype])
 
 
-@pytest.mark.parametrize("name", TINY + [WAVE] + FUSED)
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY + FUSED)
 def test_dtype_round_trip_on_one_model(name):
     """fp32 -> bf16 -> fp16 -> fp32 inputs on one model: every leg equals the cold model in that dtype, the last the first"""
     cfg = config(name)
@@ -247,7 +248,7 @@ def check_rows_do_not_see_each_other(name, dtype, B=4):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", TINY + [WAVE])
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY)
 def test_images_of_a_batch_do_not_see_each_other_tiny(name, dtype):
     """batch X with an all-NaN image at position j (first, last, middle), batch X' with a finite image there, the same batch size: every
     other row is finite and bit-equal -- stat_group, per-sample GroupNorm statistics, SplitAttention's per-image sums and the by-product
@@ -325,6 +326,24 @@ def _first(model, cls):
     return [m for m in model.modules() if type(m) is cls][0]
 
 
+class WithOffset(nn.Module):
+    """ATMLayer as a one-argument callable: the offsets are a fixed tensor"""
+
+    def __init__(self, layer, offset):
+        super().__init__()
+        self.layer = layer
+        self.register_buffer("offset", offset)
+
+    def forward(self, x):
+        return self.layer(x, self.offset.to(x.dtype))
+
+
+def _atm(B, H, W, C):
+    """ATMLayer(C) on x (B, H, W, C) with offsets (B, 2C, H, W) uniform in [-3, 3)"""
+    layer = randomize(sub("active_mlp").ATMLayer(C), 30)
+    return WithOffset(layer, torch.rand((B, 2 * C, H, W), generator=gen(130)) * 6.0 - 3.0)
+
+
 # label -> () -> (root module to move to the GPU, the module to call, its input).  The shapes are those of the
 # test_*callable_like_the_reference tests of test_gpu_models.py.
 STANDALONE = {
@@ -395,12 +414,20 @@ STANDALONE = {
     "sparse.patch_merge": lambda: (lambda m: (m, m.layers[0].patch_merge[1], rnd(2, *_geom(m.layers[0])[:3])))(_tiny("sparsemlp")),
     "wave.block": lambda: (lambda m: (m, m.network[0][0], rnd(2, 64, 16, 12)))(_tiny(WAVE)),
     "wave.patm": lambda: (lambda m: (m, m.network[0][0].attn, rnd(2, 64, 16, 12)))(_tiny(WAVE)),
+    # the shapes of `blocks` / `block_inputs` in tests/golden/raft_mlp.npz and of `blocks` in active_mlp.npz
+    "raft.permuted": lambda: (lambda m: (m, m, rnd(2, 108, 14)))(randomize(sub("raft_mlp").PermutedBlock(7, 24, 2), 28)),
+    "raft.separated": lambda: (lambda m: (m, m, rnd(2, 216, 7)))(randomize(sub("raft_mlp").SpatiallySeparatedTokenBlock(7, 24), 29)),
+    "raft.channel": lambda: (lambda m: (m, m, rnd(2, 9, 24)))(randomize(sub("raft_mlp").ChannelBlock(24), 31)),
+    "active.atm": lambda: (lambda m: (m, m, rnd(3, 5, 7, 16)))(_atm(3, 5, 7, 16)),
 }
 # the leaf modules of tests/golden/leaf_modules.npz (Hire-MLP's PreNormResidual halves and HireMLPBlock, Sparse-MLP's thirds and sMLPBlock,
 # ConvMixer's Residual, ViP's ParallelSum), on the inputs the reference fed them
 LEAF_TAGS = ["hiremlp", "sparsemlp", "convmixer", "vip_unweighted"]
 # EngineModule subclasses that are bases only: never instantiated by a constructor of the package
-BASES = {"EngineModule", "SubModule", "_SubModule", "PreNormResidualMLP", "LinearMlp", "_PermutatorBase"}
+BASES = {"EngineModule", "SubModule", "_SubModule", "PreNormResidualMLP", "LinearMlp", "_PermutatorBase",
+         "raft_mlp.Block", "raft_mlp._RaftBlock"}                  # (with its module where another family has a concrete class of that name)
+# EngineModule subclasses that constructors do instantiate, but only to hold parameters: calling one raises NotImplementedError
+HOLDERS = {"raft_mlp.TokenBlock": lambda: (sub("raft_mlp").TokenBlock(5, 12), rnd(2, 12, 5))}
 
 
 def engine_spaces(*mods):
@@ -459,7 +486,7 @@ def check_callers_own(root, mod, x):
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", TINY + [WAVE] + [t + AT224 for t in ("mixer_b16", "asmlp_t", "vip_s7")])
+@pytest.mark.parametrize("name", TINY + EVAL_ONLY + [t + AT224 for t in ("mixer_b16", "asmlp_t", "vip_s7")])
 def test_results_and_inputs_are_the_callers_full_models(name, dtype):
     """o1 unchanged by later forwards and disjoint from every workspace buffer; the input bit-identical after the call; a strided batch
     slice and a channels_last image batch give the bits of their contiguous copies"""
@@ -502,10 +529,17 @@ def test_every_engine_module_class_is_in_the_standalone_table():
                 if isinstance(obj, type) and issubclass(obj, E.EngineModule) and obj.__module__.startswith(prefix):
                     defined.add(obj)
     assert len(defined) > 30
-    called = {type(config(n).fresh()) for n in TINY + [WAVE]}
+    called = {type(config(n).fresh()) for n in TINY + EVAL_ONLY}
     for label in STANDALONE:
-        called.add(type(STANDALONE[label]()[1]))
-    missing = sorted(c.__module__.rsplit(".", 1)[1] + "." + c.__name__ for c in defined - called if c.__name__ not in BASES)
+        mod = STANDALONE[label]()[1]
+        called.add(type(mod.layer if isinstance(mod, WithOffset) else mod))
+    labels = {c: c.__module__.rsplit(".", 1)[1] + "." + c.__name__ for c in defined}
+    for label, make in HOLDERS.items():                            # on the CPU: nothing is launched
+        holder, x = make()
+        assert labels.get(type(holder)) == label
+        with pytest.raises(NotImplementedError):
+            holder(x)
+    missing = sorted(labels[c] for c in defined - called if c.__name__ not in BASES and labels[c] not in BASES | set(HOLDERS))
     assert not missing, "EngineModule subclasses without a row in test_gpu_lifecycle.STANDALONE: %s" % missing
 
 
@@ -599,7 +633,7 @@ def test_two_backwards_without_zero_grad_give_twice_the_gradient(name):
 
 # ------------------------------------------------------------------ 6. two streams
 @pytest.mark.parametrize("name,dtype", [("mixer", "bf16"), ("hiremlp", "bf16"), ("swinmlp_ape", "fp32"), ("mixer_b16" + AT224, "bf16"),
-                                        ("asmlp_t" + AT224, "bf16"), ("vip_s7" + AT224, "bf16")])
+                                        ("asmlp_t" + AT224, "bf16"), ("vip_s7" + AT224, "bf16"), ("raftmlp", "bf16"), ("activemlp", "bf16")])
 def test_two_streams_give_the_serial_results_and_see_a_weight_update(name, dtype):
     """InFlight(model, 2) on alternating different inputs: each result equals the serial one; after synchronize() a load_state_dict is
     seen by both slots (each stream has its own workspace, the packed weights are shared)"""
@@ -631,7 +665,7 @@ def test_two_streams_give_the_serial_results_and_see_a_weight_update(name, dtype
 
 # ------------------------------------------------------------------ 7. copies
 @pytest.mark.parametrize("name,dtype", [("hiremlp", "fp32"), ("hiremlp", "bf16"), ("mixer", "fp32"), ("mixer", "bf16"), ("hiremlp_s" + AT224, "bf16"),
-                                        ("mixer_b16" + AT224, "bf16")])
+                                        ("mixer_b16" + AT224, "bf16"), ("raftmlp", "bf16"), ("activemlp", "bf16")])
 def test_deepcopy_and_pickle_of_a_warm_model(name, dtype):
     """copy.deepcopy and torch.save / torch.load (through BytesIO) of a model that has run (Hire-MLP's workspace holds torch.cuda.Events):
     both work, give the warm model's bits, carry no cache, and an update of one copy leaves the other models untouched"""

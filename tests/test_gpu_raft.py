@@ -362,26 +362,6 @@ def test_deterministic_and_in_flight(meta):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
-@pytest.mark.parametrize("what", ["model", "model_nogap", "permuted", "separated", "channel"])
-def test_results_and_inputs_are_the_callers(what, dtype, meta):
-    """tests/test_gpu_lifecycle.py's ownership check (`check_callers_own`) on RaftMLP and on each block that is callable on its own: the result
-    survives later forwards and shares no storage with a workspace, the input is not written, a strided batch slice and a channels_last batch
-    give the bits of their contiguous copies.  (That file's table of EngineModule classes cannot be extended from here.)"""
-    from test_gpu_lifecycle import check_callers_own
-    rm = mp().raft_mlp
-    if what.startswith("model"):
-        model, x = tiny_model(meta, "ser_pm_nogap" if what == "model_nogap" else "ser_pm")
-        x = torch.cat([x, x.flip(0)[:1]])
-        assert check_callers_own(model, model, x.to(dtype)) >= 1
-        return
-    name = {"permuted": "permuted_7_24_2", "separated": "separated_7_24", "channel": "channel_24"}[what]
-    cls, args, _ = meta["blocks"][name]
-    blk = load_portable(getattr(rm, cls)(*args), meta["block_seed"]).to(DEV).eval()
-    x = torch.from_numpy(portable_input(tuple(meta["block_inputs"][name]), seed=3)).to(DEV).to(dtype)
-    check_callers_own(blk, blk, x)
-
-
-@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
 def test_weight_update_reaches_the_next_forward(dtype, meta):
     """packed weights follow the parameters: an in-place update of a raft block's LayerNorm weight, of its second Linear and of the classifier
     bias each changes the next forward to what a freshly built model with those weights gives"""

@@ -8,9 +8,10 @@ and buffer -- changes.  Nothing here launches a kernel: the models stay on the C
     documentation and the code cannot drift apart -- and `invalidate_caches()` empties `_packs` / `_spaces` of the module and of every
     nested EngineModule and drops the module's entries of autograd._PACKS, and no other model's.
 
-Configurations.  TINY: one entry per family from tests/golden/tiny_*.npz (built through test_gpu_models.build_from_tiny) and WaveMLP-T
-from tests/golden/wave_mlp.npz's meta (eval only).  FUSED: the constructor kwargs of tests/golden/train_grad_widths.npz -- benchmark
-widths at reduced depth -- with oracle.portable_init weights."""
+Configurations.  TINY: one entry per family from tests/golden/tiny_*.npz (built through test_gpu_models.build_from_tiny).  EVAL_ONLY: the
+families without a train path, on the tiny configurations of their own fixtures -- WaveMLP-T (wave_mlp.npz's meta), RaftMLP ser_pm with the
+gap=True and the gap=False head (raft_mlp.npz) and ActiveMLP s64 with widened offset biases (active_mlp.npz).  FUSED: the constructor kwargs
+of tests/golden/train_grad_widths.npz -- benchmark widths at reduced depth -- with oracle.portable_init weights."""
 import copy
 import functools
 import inspect
@@ -28,11 +29,13 @@ from oracle.portable_init import portable_input, portable_state_dict
 
 TINY = ["mixer", "gmlp", "resmlp", "vip_weighted", "s2mlpv1", "s2mlpv2", "asmlp", "convmixer", "sparsemlp", "hiremlp", "msmlp", "swinmlp_ape",
         "cyclemlp"]
-WAVE = "wavemlp"                                   # eval only: WaveMLP has no train path
+WAVE = "wavemlp"
+EVAL_ONLY = [WAVE, "raftmlp", "raftmlp_nogap", "activemlp"]       # inference-only families: no train path
 AT224 = "@224"                                     # suffix of the FUSED rows (tiny_s2mlpv2.npz and the benchmark S2-MLPv2 share a tag)
 FUSED = [t + AT224 for t in ("mixer_b16", "gmlp_s", "resmlp_24", "vip_s7", "s2mlpv2", "asmlp_t", "convmixer_1536_20", "sparsemlp_t", "hiremlp_s",
                              "msmlp_t", "swinmlp_t", "cyclemlp_b1")]
 BN_FAMILIES = {"convmixer", "sparsemlp", "convmixer_1536_20" + AT224, "sparsemlp_t" + AT224}       # train mode moves running statistics
+HOLDS_BATCHNORM = BN_FAMILIES | {WAVE}             # the rows with a BatchNorm module (WaveMLP's never leaves eval mode)
 _CACHE = {}
 
 
@@ -72,6 +75,18 @@ def config(name):
         meta = json.loads(str(np.load(os.path.join(GOLDEN, "wave_mlp.npz"))["meta"]))
         ctor, kw, hw, classes, seed = functools.partial(pkg.models_pytorch.WaveMLP, "T"), {"num_classes": 10}, tuple(meta["tiny_hw"]), 10, meta["tiny_seed"]
         sd = _portable(ctor(**kw), seed)
+    elif name in ("raftmlp", "raftmlp_nogap"):
+        meta = json.loads(str(np.load(os.path.join(GOLDEN, "raft_mlp.npz"))["meta"]))
+        kw = dict(meta["tiny_cases"]["ser_pm" if name == "raftmlp" else "ser_pm_nogap"], num_classes=10)
+        ctor, hw, classes = functools.partial(pkg.models_pytorch.RaftMLP, meta["tiny"]), (kw["image_size"],) * 2, 10
+        sd = _portable(ctor(**kw), meta["tiny_seed"])
+    elif name == "activemlp":
+        from test_gpu_active import load_portable, widen           # the state test_gpu_active.tiny_model builds for its s64 case
+        meta = json.loads(str(np.load(os.path.join(GOLDEN, "active_mlp.npz"))["meta"]))
+        ctor, kw, hw, classes = pkg.models_pytorch.ActiveMLP, dict(meta["tiny"]), tuple(meta["tiny_cases"]["s64"]["size"]), meta["tiny"]["num_classes"]
+        model = load_portable(ctor(**kw), meta["tiny_seed"])
+        widen(model, meta, meta["tiny_seed"])                      # offset biases in [-3, 3): the sampler sees real offsets
+        sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
     elif name in FUSED:
         z = np.load(os.path.join(GOLDEN, "train_grad_widths.npz"))
         tag = name[:-len(AT224)]
@@ -188,7 +203,7 @@ def adamw(params):
 
 
 # ------------------------------------------------------------------ the host tests
-HOST = TINY + [WAVE]
+HOST = TINY + EVAL_ONLY
 
 
 @pytest.mark.parametrize("name", HOST)
@@ -203,7 +218,7 @@ def test_param_stamp_sees_every_visible_update_form(name):
     # ... moving BatchNorm's running statistics the way a train-mode forward does (in-place writes to buffers under no_grad)
     m = cfg.fresh()
     bns = [b for b in m.modules() if isinstance(b, nn.modules.batchnorm._BatchNorm)]
-    assert bool(bns) == (name in BN_FAMILIES or name == WAVE), name
+    assert bool(bns) == (name in HOLDS_BATCHNORM), name
     if bns:
         before = m._param_stamp()
         with torch.no_grad():
@@ -304,7 +319,7 @@ def _fill_caches(pkg, m, marker):
     return mods
 
 
-@pytest.mark.parametrize("name", ["mixer", "resmlp", "hiremlp", "msmlp", WAVE])
+@pytest.mark.parametrize("name", ["mixer", "resmlp", "hiremlp", "msmlp", WAVE, "raftmlp", "activemlp"])
 def test_invalidate_caches_empties_the_module_tree_and_its_train_packs(pkg, name):
     E, AG = pkg.engine, importlib_autograd(pkg)
     cfg = config(name)
@@ -337,7 +352,7 @@ def importlib_autograd(pkg):
     return importlib.import_module(pkg.__name__ + ".autograd")
 
 
-@pytest.mark.parametrize("name", ["mixer", "hiremlp"])
+@pytest.mark.parametrize("name", ["mixer", "hiremlp", "raftmlp", "activemlp"])
 def test_copies_and_pickles_travel_without_the_caches(pkg, name):
     """copy.deepcopy and torch.save(model) carry parameters, buffers and settings, not packed weights or workspaces; the original keeps
     its own; the block -> backbone links of the copy point into the copy"""
