@@ -61,6 +61,9 @@
  *   mlpk_raft_gather_ln, mlpk_raft_scatter_add   RaftMLP's raft token mixing (raft_mlp.py:114-146,333-362): LayerNorm + the re-layout into the
  *                       token MLP's operand rows, and the residual addition of its result back onto the map; the MLP itself is
  *                       mlpk_channel_mlp or two mlpk_gemm_nt
+ *   mlpk_dyna_mix       DynaMixer's dynamic token mixing along one axis (dyna_mlp.py:34-94): the attend Linear, the softmax and the L x L mix of
+ *                       LayerNorm(x) per image, line and channel segment in one kernel; logits and LayerNorm(x) never reach memory
+ *   mlpk_dyna_gather, mlpk_dyna_mix_logits   the same operation around an ordinary GEMM for the logits (the unfused form)
  *   mlpk_dwconv_nhwc    depthwise Conv2d(k, groups=dim, padding="same") + GELU + BatchNorm(eval) + residual:
  *                       conv_mixer.py:5-11,24-28
  */
@@ -794,6 +797,46 @@ int mlpk_atm_sample(int dtype, const void* x, int64_t x_pitch, const float* mean
                     const void* off, int64_t off_pitch, int share, void* out_w, void* out_h, void* out_c, int64_t out_pitch, int B, int H, int W,
                     int C, void* stream);
 int mlpk_atm_tap(float off, int pos, int L, int* i0, int* i1, float* w0, float* w1);
+
+/* DynaMixer's dynamic token mixing along ONE axis (DynaMixerOp_h dyna_mlp.py:65-94, DynaMixerOp_w :34-63) without its two Linears `Wd` and `proc`.
+ * x: channel-last rows of the (B, H, W) map at row pitch x_pitch >= C; the operand is xn[pix, c] = round_to_storage((x[pix, c] - mean[pix]) rstd[pix]
+ * gamma[c] + beta[c]), the expression and rounding of mlpk_norm_apply, never stored on its own.  mean / rstd per pixel (B H W), both NULL: 0 / 1;
+ * gamma / beta per channel, NULL: 1 / 0.  axis 0 (DynaMixerOp_h): a line is a column, L = H, pix(l) = (b H + l) W + q, q < W; axis 1
+ * (DynaMixerOp_w): a line is a row, L = W, pix(l) = (b H + q) W + l, q < H.  s = segment, d = C / s, hd = hidden_dim_DMO.
+ * t: rows (B H W, >= t_off + s hd) of the storage type at row pitch t_pitch: columns [t_off + g hd, t_off + (g + 1) hd) are Wd[g](xn), the
+ * concatenation of :54-57 / :85-88 as it lies (both axes may share one buffer at different t_off).  Per (b, line, segment g):
+ *   v[l hd + j]      = t[pix(l), t_off + g hd + j]                                   Rearrange 'b h w (s d) -> b h s (w d)' (:42 / :73)
+ *   z[l1 L + l2]     = ab[l1 L + l2] + sum_k A[l1 L + l2][k] v[k], K = L hd          attend.1 (:43 / :74), fp32 accumulation
+ *   p[l1][l2]        = exp(z[l1 L + l2] - max_l2) / sum_l2 exp(..)                   Softmax(dim = -1) (:45 / :76), fp32, the row maximum subtracted
+ *   out[pix(l1), g d + c] = round(sum_l2 p[l1][l2] xn[pix(l2), g d + c])             torch.matmul(attn, input) + recover (:61-62 / :92-93), fp32 sum
+ * aw: attend.1's weight A (L L, K) in the storage type, packed as [ceil(K / e)][L L][e] with e = elements per 16 bytes (8 for 16-bit, 4 for fp32),
+ * element [k / e][n][k % e] = A[n][k], zeros for k >= K (engine.pack_dyna_attend); ab: its bias, fp32 (L L).  out: rows at pitch out_pitch >= C
+ * (a column block of a wider buffer is fine); columns at or beyond C of an output row are not touched.  Images, lines and segments are independent:
+ * a NaN in one image changes no bit of another.  A row of p whose logits are 0 and -200 is exactly one-hot, and out then holds xn's bits.
+ * Returns before anything touches a device: a missing pointer (or only one of mean / rstd) MLPK_ENULL; a dtype other than fp32 / fp16 / bf16
+ * MLPK_EDTYPE; a non-positive extent, axis not 0 / 1, L > 32, L hd > 256, C % s != 0, d not a whole number of 16-byte vectors (d % 8 for 16-bit,
+ * d % 4 for fp32), x_pitch < C, out_pitch < C, t_off < 0 or t_pitch < t_off + s hd MLPK_ESHAPE; x, out, aw, x_pitch or out_pitch off a 16-byte
+ * boundary, t not aligned to its element or ab to 4 bytes MLPK_EALIGN.
+ * mlpk_dyna_mix_supported: 1 exactly where the entry accepts the dtype and the shape (L = the extent of the axis), else 0.  The results do not
+ * depend on the pitches. */
+int mlpk_dyna_mix_supported(int dtype, int L, int C, int s, int hd);
+int mlpk_dyna_mix(int dtype, const void* x, int64_t x_pitch, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                  const void* t, int64_t t_pitch, int t_off, const void* aw, const float* ab, void* out, int64_t out_pitch, int B, int H, int W,
+                  int C, int s, int hd, int axis, void* stream);
+
+/* The UNFUSED form of mlpk_dyna_mix, the product path of the 16-bit types where an ordinary GEMM makes the logits (profiles/dyna_mix_fused_vs_unfused.jsonl):
+ *   mlpk_dyna_gather      v[item, l hd + j] = t[pix(l), t_off + g hd + j], item = (b Q + q) s + g in mlpk_dyna_mix's item order: the GEMM's operand rows
+ *                         (B Q s, kp) at row pitch v_pitch >= kp >= L hd; columns [L hd, kp) are written as zeros, columns beyond kp are not touched.
+ *   (mlpk_gemm_nt)        z[item, l1 L + l2] = ab + A v, rows of the storage type at row pitch z_pitch >= L L
+ *   mlpk_dyna_mix_logits  the softmax over l2 and the mix of LayerNorm(x) exactly as mlpk_dyna_mix does them (one device function, csrc/mlpk_dyna.h), the
+ *                         logits read from z and widened to fp32.  Columns of z at or beyond L L are never read.
+ * x, mean, rstd, gamma, beta, out, the axes, the supported shapes (mlpk_dyna_mix_supported) and the error codes are mlpk_dyna_mix's; additionally
+ * kp < L hd, v_pitch < kp, z_pitch < L L or B Q s L >= 2^31 (gather) MLPK_ESHAPE; t, v, z not aligned to their element MLPK_EALIGN.  The gather
+ * takes any s and hd with L <= 32 and L hd <= 256.  Both return before anything touches a device. */
+int mlpk_dyna_gather(int dtype, const void* t, int64_t t_pitch, int t_off, void* v, int64_t v_pitch, int kp, int B, int H, int W, int s, int hd, int axis,
+                     void* stream);
+int mlpk_dyna_mix_logits(int dtype, const void* x, int64_t x_pitch, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                         const void* z, int64_t z_pitch, void* out, int64_t out_pitch, int B, int H, int W, int C, int s, int hd, int axis, void* stream);
 
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that

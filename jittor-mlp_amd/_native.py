@@ -161,6 +161,13 @@ PROTOTYPES = {
     "mlpk_atm_sample": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_int] + [c_void_p] * 3 + [c_i64] + [c_int] * 4 + [c_void_p]),
     # (off, pos, L, i0, i1, w0, w1)
     "mlpk_atm_tap": (c_int, [ctypes.c_float, c_int, c_int] + [c_void_p] * 4),
+    "mlpk_dyna_mix_supported": (c_int, [c_int] * 5),
+    # (dtype, t, t_pitch, t_off, v, v_pitch, kp, B, H, W, s, hd, axis, stream)
+    "mlpk_dyna_gather": (c_int, [c_int, c_void_p, c_i64, c_int, c_void_p, c_i64] + [c_int] * 7 + [c_void_p]),
+    # (dtype, x, x_pitch, mean, rstd, gamma, beta, z, z_pitch, out, out_pitch, B, H, W, C, s, hd, axis, stream)
+    "mlpk_dyna_mix_logits": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_void_p, c_i64] + [c_int] * 7 + [c_void_p]),
+    # (dtype, x, x_pitch, mean, rstd, gamma, beta, t, t_pitch, t_off, aw, ab, out, out_pitch, B, H, W, C, s, hd, axis, stream)
+    "mlpk_dyna_mix": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_int] + [c_void_p] * 3 + [c_i64] + [c_int] * 7 + [c_void_p]),
 }
 
 _lib = None

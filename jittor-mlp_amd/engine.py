@@ -759,6 +759,62 @@ def atm_sample(x, mean, rstd, gamma, beta, off, share, out_w, out_h, out_c, B, H
                                     ptr(out_w), ptr(out_h), ptr(out_c), ref.stride(0), B, H, W, C, stream()), "mlpk_atm_sample")
 
 
+def dyna_mix_supported(dtype, L, C, s, hd):
+    return bool(N.lib().mlpk_dyna_mix_supported(dtype_code(dtype), L, C, s, hd))
+
+
+def pack_dyna_attend(w, b, dtype, device):
+    """DynaMixerOp's attend.1, weight (L L, K = L hd) and bias (L L) -> mlpk_dyna_mix's operands: the weight in the storage type as
+    [ceil(K / e)][L L][e], e = elements per 16 bytes, zeros for k >= K (thread n of the kernel reads e consecutive k of its output column in
+    one load, and consecutive threads read consecutive 16-byte pieces; in the 16-bit types the same 16 bytes are a lane's A fragment of the
+    matrix instruction: csrc/mlpk_dyna.hip); the bias fp32"""
+    w = w.detach().to(device=device, dtype=torch.float32).reshape(w.shape[0], -1)
+    n, k = w.shape
+    e = 4 if dtype == torch.float32 else 8
+    kp = round_up(k, e)
+    wp = torch.zeros((n, kp), dtype=dtype, device=device)
+    wp[:, :k] = w.to(dtype)
+    return wp.view(n, kp // e, e).permute(1, 0, 2).contiguous(), f32(b, device)
+
+
+def dyna_mix(x, mean, rstd, gamma, beta, t, t_off, aw, ab, out, B, H, W, C, s, hd, axis):
+    """DynaMixer's dynamic token mixing along one axis (mlpk_dyna_mix; axis 0 = DynaMixerOp_h, 1 = DynaMixerOp_w): out (a column block of a
+    wider buffer is fine) = softmax(attend.1(t's columns [t_off, t_off + s hd) along the line)) applied to LayerNorm(x) per segment"""
+    N.check(N.lib().mlpk_dyna_mix(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(t), t.stride(0), t_off,
+                                  ptr(aw), ptr(ab), ptr(out), out.stride(0), B, H, W, C, s, hd, axis, stream()), "mlpk_dyna_mix")
+
+
+def dyna_unfused_preferred(dtype, L):
+    """where the model takes the unfused form (dyna_mix_unfused) instead of mlpk_dyna_mix: the 16-bit types, lines of 8 to 32 positions in whole
+    16-byte rows of logits -- the range the alternating measurement covers (profiles/dyna_mix_fused_vs_unfused.jsonl: 7-20 % faster at L = 16 and
+    32, the gather included); shorter lines, whose GEMM would be a few columns wide, and fp32 stay on the fused kernel"""
+    return dtype in (torch.float16, torch.bfloat16) and L >= 8 and (L * L) % 8 == 0
+
+
+def dyna_gather(t, t_off, v, kp, B, H, W, s, hd, axis):
+    """the operand rows of the logits GEMM, v[(b, q, g), l hd + j] = t[pix(l), t_off + g hd + j], zeros in columns [L hd, kp) (mlpk_dyna_gather)"""
+    N.check(N.lib().mlpk_dyna_gather(dtype_code(t.dtype), ptr(t), t.stride(0), t_off, ptr(v), v.stride(0), kp, B, H, W, s, hd, axis, stream()),
+            "mlpk_dyna_gather")
+
+
+def dyna_mix_logits(x, mean, rstd, gamma, beta, z, out, B, H, W, C, s, hd, axis):
+    """mlpk_dyna_mix's softmax and mix on logits z (items, >= L L) that a GEMM wrote (mlpk_dyna_mix_logits)"""
+    N.check(N.lib().mlpk_dyna_mix_logits(dtype_code(x.dtype), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(z), z.stride(0),
+                                         ptr(out), out.stride(0), B, H, W, C, s, hd, axis, stream()), "mlpk_dyna_mix_logits")
+
+
+def dyna_mix_unfused(ws, tag, x, mean, rstd, gamma, beta, t, t_off, awr, ab, out, B, H, W, C, s, hd, axis):
+    """the unfused form of dyna_mix: gather, the logits as one GEMM (awr = attend.1's weight row-major, pack_matrix) into a buffer of the storage
+    type, then the softmax and the mix.  ws / tag name the two workspace buffers."""
+    L, Q = (W, H) if axis == 1 else (H, W)
+    items, kp, nn = B * Q * s, awr.shape[1], L * L
+    v = ws.get("%s.v%d" % (tag, axis), (items, kp))
+    z = ws.get("%s.z%d" % (tag, axis), (items, round_up(nn, 8)))
+    dyna_gather(t, t_off, v, kp, B, H, W, s, hd, axis)
+    gemm(v, awr, z, items, nn, kp, bias=ab, tag="dyna_logits")
+    dyna_mix_logits(x, mean, rstd, gamma, beta, z, out, B, H, W, C, s, hd, axis)
+
+
 def dwconv_plain_nhwc(x, out, B, H, W, C, k, w, bias):
     """depthwise Conv2d(k, groups = C, padding = "same") on dense channel-last rows, no epilogue (mlpk_dwconv_plain_nhwc): w fp32 [k * k][C]"""
     N.check(N.lib().mlpk_dwconv_plain_nhwc(dtype_code(x.dtype), 0, ptr(x), ptr(out), B, H, W, C, k, ptr(w), ptr(bias), stream()), "mlpk_dwconv_plain_nhwc")
