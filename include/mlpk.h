@@ -64,6 +64,8 @@
  *   mlpk_dyna_mix       DynaMixer's dynamic token mixing along one axis (dyna_mlp.py:34-94): the attend Linear, the softmax and the L x L mix of
  *                       LayerNorm(x) per image, line and channel segment in one kernel; logits and LayerNorm(x) never reach memory
  *   mlpk_dyna_gather, mlpk_dyna_mix_logits   the same operation around an ordinary GEMM for the logits (the unfused form)
+ *   mlpk_lstm_scan      Sequencer2D's BiLSTM2D recurrence (sequencer.py:31-46): one bidirectional LSTM along one axis of the map, W_hh resident
+ *                       in registers, the h W_hh product of every step on the matrix pipe
  *   mlpk_dwconv_nhwc    depthwise Conv2d(k, groups=dim, padding="same") + GELU + BatchNorm(eval) + residual:
  *                       conv_mixer.py:5-11,24-28
  */
@@ -837,6 +839,34 @@ int mlpk_dyna_gather(int dtype, const void* t, int64_t t_pitch, int t_off, void*
                      void* stream);
 int mlpk_dyna_mix_logits(int dtype, const void* x, int64_t x_pitch, const float* mean, const float* rstd, const float* gamma, const float* beta,
                          const void* z, int64_t z_pitch, void* out, int64_t out_pitch, int B, int H, int W, int C, int s, int hd, int axis, void* stream);
+
+/* Sequencer2D's BiLSTM2D recurrence (sequencer.py:31-46): ONE bidirectional LSTM (nn.LSTM(num_layers = 1, batch_first, bidirectional)) along ONE
+ * axis of a channel-last (B, H, W) map, after its input projections.  axis 0 (`rnn_v`): a sequence is a column, L = H, pix(l) = (b H + l) W + q,
+ * one sequence per (b, q < W); axis 1 (`rnn_h`): a sequence is a row, L = W, pix(l) = (b H + q) W + l, q < H.  Pixels are addressed by strides:
+ * no permuted copy of the map exists (:40-43).
+ * xp: rows (B H W) of the storage type at row pitch xp_pitch; columns [xp_off, xp_off + 8 hid) hold [forward: i f g o | reverse: i f g o], each hid
+ * wide, = W_ih x + b_ih + b_hh in torch's gate order, as a GEMM's epilogue left them.  whh: weight_hh_l0 and weight_hh_l0_reverse, each (4 hid, hid)
+ * row-major in the storage type, one after the other: element [d][g hid + j][k] (engine.pack_lstm_hh; a workgroup's waves keep their rows in
+ * registers for the whole sequence).  Per sequence and direction d, t = 0 .. L - 1, l = t (forward) or L - 1 - t (reverse), h_{-1} = c_{-1} = 0:
+ *   z        = float(xp[pix(l), xp_off + 4 d hid + ..]) + W_hh[d] h_{t-1}     fp32 accumulation (fp32: v_mfma_f32_16x16x4_f32; 16-bit: the K = 16
+ *                                                                            matrix instruction, hid = 48 without padding)
+ *   c_t      = sigmoid(z_f) c_{t-1} + sigmoid(z_i) tanh(z_g)                  fp32, in registers for the whole sequence
+ *   h_t      = round_to_storage(sigmoid(z_o) tanh(c_t))                       rounded ONCE: the stored value is the next step's operand
+ *   out[pix(l), out_off + d hid + j] = h_t[j]
+ * which is the output of nn.LSTM in the reference's layout (:41, :43): `v` and `h` of a block land in the two halves of one (rows, 4 hid) buffer
+ * through out_off, and torch.cat (:44) costs nothing.  Columns outside [out_off, out_off + 2 hid) of an output row are not touched.  Every finite
+ * pre-activation gives a finite result (an overflowing exp ends in 0 or 1, never in inf - inf).  sigmoid and tanh: fp32 storage evaluates them in
+ * fp64 and rounds once; the 16-bit types use the hardware exp2 and reciprocal in fp32.  Sequences do not see each other: a NaN in one changes no
+ * bit of another.  The results depend neither on the pitches or offsets nor on where in the map (in which workgroup and lane) a sequence lies.
+ * Takes hid = 16, 32, 48, 96, every L >= 1 and any B, H, W in fp32, fp16 and bf16; mlpk_lstm_scan_supported is 1 exactly there.
+ * Vector accesses: 4 elements (8 bytes in the 16-bit types, 16 in fp32) of xp and out, so xp, out and whh must lie on 16-byte boundaries and the
+ * pitches and column offsets must be multiples of 4 elements.
+ * Returns before anything touches a device: a missing pointer MLPK_ENULL; a dtype other than fp32 / fp16 / bf16 MLPK_EDTYPE; a non-positive extent,
+ * axis not 0 / 1, hid outside the set, a negative offset, xp_pitch < xp_off + 8 hid, out_pitch < out_off + 2 hid MLPK_ESHAPE; xp, out or whh off a
+ * 16-byte boundary, a pitch or an offset that is not a multiple of 4 elements, or the span read of xp overlapping the span written of out MLPK_EALIGN. */
+int mlpk_lstm_scan_supported(int dtype, int L, int hid);
+int mlpk_lstm_scan(int dtype, const void* xp, int64_t xp_pitch, int xp_off, const void* whh, void* out, int64_t out_pitch, int out_off, int B, int H,
+                   int W, int hid, int axis, void* stream);
 
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that

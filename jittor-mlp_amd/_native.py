@@ -168,6 +168,9 @@ PROTOTYPES = {
     "mlpk_dyna_mix_logits": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_void_p, c_i64] + [c_int] * 7 + [c_void_p]),
     # (dtype, x, x_pitch, mean, rstd, gamma, beta, t, t_pitch, t_off, aw, ab, out, out_pitch, B, H, W, C, s, hd, axis, stream)
     "mlpk_dyna_mix": (c_int, [c_int, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64, c_int] + [c_void_p] * 3 + [c_i64] + [c_int] * 7 + [c_void_p]),
+    "mlpk_lstm_scan_supported": (c_int, [c_int] * 3),
+    # (dtype, xp, xp_pitch, xp_off, whh, out, out_pitch, out_off, B, H, W, hid, axis, stream)
+    "mlpk_lstm_scan": (c_int, [c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_i64, c_int] + [c_int] * 5 + [c_void_p]),
 }
 
 _lib = None

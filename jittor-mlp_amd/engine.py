@@ -815,6 +815,29 @@ def dyna_mix_unfused(ws, tag, x, mean, rstd, gamma, beta, t, t_off, awr, ab, out
     dyna_mix_logits(x, mean, rstd, gamma, beta, z, out, B, H, W, C, s, hd, axis)
 
 
+def lstm_scan_supported(dtype, L, hid):
+    return bool(N.lib().mlpk_lstm_scan_supported(dtype_code(dtype), L, hid))
+
+
+def pack_lstm_hh(w_fwd, w_rev, dtype, device):
+    """the two weight_hh matrices of a bidirectional nn.LSTM, each (4 hid, hid) -> mlpk_lstm_scan's `whh`: (2, 4 hid, hid) in the storage type,
+    [forward | reverse], row-major as torch holds them (rows in gate order i f g o)"""
+    out = torch.stack([w_fwd.detach().to(device=device, dtype=torch.float32), w_rev.detach().to(device=device, dtype=torch.float32)], 0)
+    return out.to(dtype).contiguous()
+
+
+def unpack_lstm_hh(whh):
+    """(weight_hh, weight_hh_reverse) of a pack_lstm_hh result, in the packed type"""
+    return whh[0], whh[1]
+
+
+def lstm_scan(xp, xp_off, whh, out, out_off, B, H, W, hid, axis):
+    """one bidirectional LSTM along one axis of the (B, H, W) map (mlpk_lstm_scan; axis 0 = BiLSTM2D.rnn_v, 1 = rnn_h): columns [xp_off,
+    xp_off + 8 hid) of xp are the input projections of both directions, the hidden states go to columns [out_off, out_off + 2 hid) of out"""
+    N.check(N.lib().mlpk_lstm_scan(dtype_code(xp.dtype), ptr(xp), xp.stride(0), xp_off, ptr(whh), ptr(out), out.stride(0), out_off, B, H, W, hid,
+                                   axis, stream()), "mlpk_lstm_scan")
+
+
 def dwconv_plain_nhwc(x, out, B, H, W, C, k, w, bias):
     """depthwise Conv2d(k, groups = C, padding = "same") on dense channel-last rows, no epilogue (mlpk_dwconv_plain_nhwc): w fp32 [k * k][C]"""
     N.check(N.lib().mlpk_dwconv_plain_nhwc(dtype_code(x.dtype), 0, ptr(x), ptr(out), B, H, W, C, k, ptr(w), ptr(bias), stream()), "mlpk_dwconv_plain_nhwc")
