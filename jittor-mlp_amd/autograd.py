@@ -18,6 +18,7 @@ gradients come back in fp32 whatever the compute dtype (the GEMMs accumulate in 
 import weakref
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native as N
 from . import engine as E
@@ -29,16 +30,49 @@ def _epc(dtype):
 
 def _pad_cols(t, cols):
     """(M, k) -> contiguous (M, cols) with zero columns behind k (a GEMM's K must be whole 16-byte chunks)"""
-    if t.shape[1] == cols and t.is_contiguous():
-        return t
+    if t.shape[1] == cols:
+        return _dense(t)
     out = torch.zeros((t.shape[0], cols), dtype=t.dtype, device=t.device)
     out[:, :t.shape[1]].copy_(t)
     return out
 
 
+def _copy(t):
+    """a fresh row-major copy.  Not `t.contiguous()`: torch calls every one-row view contiguous and hands it back, with the base and the row
+    stride it has -- a (1, C) slice at an odd offset, the `.t()` of a column (strides (1, 1))"""
+    return t.clone(memory_format=torch.contiguous_format)
+
+
+def _dense(t):
+    """t.contiguous() for the kernels that take no pitch, or one for all operands; a one-row view (contiguous to torch, see _copy) is copied
+    unless it is a plain row: unit column stride, a row stride of at least the width, a 16-byte aligned base"""
+    if t.dim() == 2 and t.shape[0] == 1 and not (t.stride(1) == 1 and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0):
+        return _copy(t)
+    return t.contiguous()
+
+
+def _rows(t):
+    """an operand or a gradient as the kernels of mlpk_backward.hip take it: unit column stride and a row pitch of at least the width (a
+    column slice of a wider tensor keeps its pitch and its base, whatever their alignment: those kernels use element loads).  Everything
+    else -- a transposed view, a broadcast one with row stride 0 (what `y.sum().backward()` delivers), a single row whose stride is below
+    the width (the kernels check `ld >= cols` whatever the row count) -- is copied."""
+    return t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else _copy(t)
+
+
+def _rows16(t):
+    """_rows for the kernels of mlpk_norm.hip (mlpk_row_stats, mlpk_norm_apply, mlpk_pool_mean): they want a 16-byte aligned base and a pitch of
+    whole 8-element chunks, and mlpk_row_stats sums in another order without them -- a slice that has neither is copied, so the bits
+    never depend on the layout the caller chose"""
+    t = _rows(t)
+    return t if t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0 else _copy(t)
+
+
 def transpose(x, batch, R, Cc, ld_out=None, res=None):
-    """x: (batch * R, Cc) row-major -> (batch * Cc, ld_out) with out[b, c, r] = x[b, r, c] (+ res); padding columns zero"""
+    """x: (batch * R, Cc) rows -> (batch * Cc, ld_out) with out[b, c, r] = x[b, r, c] (+ res); padding columns zero.  x and res pass through
+    _rows: mlpk_transpose_batched is told one pitch per operand and reads columns at unit stride."""
     ld_out = ld_out or R
+    x = _rows(x)
+    res = _rows(res) if res is not None else None
     out = (torch.zeros if ld_out != R else torch.empty)((batch * Cc, ld_out), dtype=x.dtype, device=x.device)
     N.check(N.lib().mlpk_transpose_batched(E.dtype_code(x.dtype), E.ptr(x), x.stride(0), E.ptr(out), ld_out, E.ptr(res), res.stride(0) if res is not None else 0,
                                            batch, R, Cc, E.stream()), "mlpk_transpose_batched")
@@ -87,6 +121,7 @@ class Linear(torch.autograd.Function):
         with E.on_device(x):
             xp = _pad_cols(x, kp)
             wp = _packed(w, w2, cd, dev, kp)
+            r = _dense(r) if r is not None else None                   # the residual epilogue is told one pitch and reads columns at unit stride
             y = torch.empty((x.shape[0], n), dtype=cd, device=dev)
             E.gemm(xp, wp, y, x.shape[0], n, kp, bias=E.f32(b, dev), R=r, res=N.RES_ADD if r is not None else N.RES_NONE)
         ctx.save_for_backward(xp, wp)
@@ -94,6 +129,7 @@ class Linear(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         xp, wp = ctx.saved_tensors
         wshape, k, xcols, has_b, has_r = ctx.meta
@@ -101,7 +137,7 @@ class Linear(torch.autograd.Function):
         m, n = dy.shape
         epc = _epc(cd)
         np_, mp = E.round_up(n, epc), E.round_up(m, epc)
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = dw = db = None
         with E.on_device(dy):
             if ctx.needs_input_grad[0]:
@@ -126,22 +162,30 @@ class Linear(torch.autograd.Function):
 
 
 class Gelu(torch.autograd.Function):
+    """exact (erf) GELU of (M, C) rows.  mlpk_gelu_elementwise applies ONE pitch to a, b and out, so all three are dense here: `pre` is copied
+    unless contiguous (torch.empty_like of a column slice is dense -- the slice's pitch on it wrote past its end), and the copy is what the
+    tape keeps.  Roundings: 1 forward, 1 backward."""
+
     @staticmethod
     def forward(ctx, pre):
-        out = torch.empty_like(pre)
+        pre = _dense(pre)
+        rows, cols = pre.shape
+        out = torch.empty((rows, cols), dtype=pre.dtype, device=pre.device)
         with E.on_device(pre):
-            N.check(N.lib().mlpk_gelu_elementwise(E.dtype_code(pre.dtype), 0, E.ptr(pre), None, E.ptr(out), pre.shape[0], pre.shape[1], pre.stride(0), E.stream()),
+            N.check(N.lib().mlpk_gelu_elementwise(E.dtype_code(pre.dtype), 0, E.ptr(pre), None, E.ptr(out), rows, cols, cols, E.stream()),
                     "mlpk_gelu_elementwise")
         ctx.save_for_backward(pre)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (pre,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = torch.empty_like(pre)
+        rows, cols = pre.shape
+        dy = _dense(dy)
+        dx = torch.empty((rows, cols), dtype=pre.dtype, device=pre.device)
         with E.on_device(pre):
-            N.check(N.lib().mlpk_gelu_elementwise(E.dtype_code(pre.dtype), 1, E.ptr(pre), E.ptr(dy), E.ptr(dx), pre.shape[0], pre.shape[1], pre.stride(0), E.stream()),
+            N.check(N.lib().mlpk_gelu_elementwise(E.dtype_code(pre.dtype), 1, E.ptr(pre), E.ptr(dy), E.ptr(dx), rows, cols, cols, E.stream()),
                     "mlpk_gelu_elementwise")
         return dx
 
@@ -153,6 +197,7 @@ class LayerNorm(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, eps):
         m, c = x.shape
         dev = x.device
+        x = _rows16(x)
         with E.on_device(x):
             mean = torch.empty((m,), dtype=torch.float32, device=dev)
             rstd = torch.empty_like(mean)
@@ -165,14 +210,15 @@ class LayerNorm(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         x, mean, rstd, g32 = ctx.saved_tensors
         m, c = x.shape
-        dy = dy.contiguous()
+        dy = _dense(dy)
         with E.on_device(x):
             nb = N.lib().mlpk_layernorm_backward_blocks(m)
             part = torch.empty((nb, 2 * c), dtype=torch.float32, device=x.device)
-            dx = torch.empty_like(x)
+            dx = torch.empty((m, c), dtype=x.dtype, device=x.device)
             N.check(N.lib().mlpk_layernorm_backward(E.dtype_code(x.dtype), E.ptr(x), x.stride(0), E.ptr(mean), E.ptr(rstd), E.ptr(g32), E.ptr(dy), dy.stride(0),
                                                     E.ptr(dx), dx.stride(0), E.ptr(part), m, c, E.stream()), "mlpk_layernorm_backward")
             sums = col_sum(part, nb, 2 * c)
@@ -181,7 +227,7 @@ class LayerNorm(torch.autograd.Function):
 
 class TokensToRows(torch.autograd.Function):
     """(B*S, C) token-major -> (B*C, S_pad): rows = (image, channel), the token axis contiguous and zero-padded to a GEMM's K
-    (the rearrange in front of the token-mixing FeedForward, mlp_mixer.py:34: Conv1d(k=1) over the patch axis)"""
+    (the rearrange in front of the token-mixing FeedForward, mlp_mixer.py:34: Conv1d(k=1) over the patch axis).  Data movement both ways: no rounding."""
 
     @staticmethod
     def forward(ctx, x, B, S):
@@ -190,15 +236,17 @@ class TokensToRows(torch.autograd.Function):
             return transpose(x, B, S, x.shape[1], ld_out=E.round_up(S, _epc(x.dtype)))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dxt):
         B, S, C = ctx.dims
-        dxt = dxt.contiguous()
+        dxt = _dense(dxt)
         with E.on_device(dxt):
             return transpose(dxt, B, C, S, ld_out=C), None, None
 
 
 class RowsToTokensAdd(torch.autograd.Function):
-    """out[b, s, c] = x[b, s, c] + y[b, c, s]: the token-mixing block's result back in token-major order, plus the residual (mlp_mixer.py:12)"""
+    """out[b, s, c] = x[b, s, c] + y[b, c, s]: the token-mixing block's result back in token-major order, plus the residual (mlp_mixer.py:12).
+    Roundings: 1 forward (the fp32 sum); backward: data movement (dy transposed, dy itself)."""
 
     @staticmethod
     def forward(ctx, y, x, B, S):
@@ -208,29 +256,33 @@ class RowsToTokensAdd(torch.autograd.Function):
             return transpose(y, B, C, S, ld_out=C, res=x)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         B, S, C = ctx.dims
-        dout = dout.contiguous()
+        dout = _dense(dout)
         with E.on_device(dout):
             return transpose(dout, B, S, C, ld_out=S), dout, None, None
 
 
 class TokenMean(torch.autograd.Function):
-    """Reduce('b n c -> b c', 'mean') (mlp_mixer.py:63)"""
+    """Reduce('b n c -> b c', 'mean') (mlp_mixer.py:63).  x passes through _rows16 (mlpk_pool_mean: C % 8 == 0).  Roundings: 1 forward, 1 backward
+    (dy * fp32(1 / S): two fp32 operations)."""
 
     @staticmethod
     def forward(ctx, x, B, S):
         C = x.shape[1]
         ctx.dims = (B, S, C)
+        x = _rows16(x)
         out = torch.empty((B, C), dtype=x.dtype, device=x.device)
         with E.on_device(x):
             E.pool_mean(x, B, S, C, x.stride(0), out, C)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, S, C = ctx.dims
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = torch.empty((B * S, C), dtype=dy.dtype, device=dy.device)
         with E.on_device(dy):
             N.check(N.lib().mlpk_broadcast_rows(E.dtype_code(dy.dtype), E.ptr(dy), E.ptr(dx), B, S, C, 1.0 / S, E.stream()), "mlpk_broadcast_rows")
@@ -281,16 +333,13 @@ def col_dot(x, y):
     return out
 
 
-def _rows(t):
-    """a gradient as the kernels take it: unit column stride (a chunk of a wider tensor keeps its row stride)"""
-    return t if t.stride(1) == 1 else t.contiguous()
-
-
 class Affine(torch.autograd.Function):
-    """y = x * alpha[c] + beta[c] on (M, C) rows: Aff (res_mlp.py:11-19), the affine half of GroupNorm / BatchNorm.  beta may be None."""
+    """y = x * alpha[c] + beta[c] on (M, C) rows: Aff (res_mlp.py:11-19), the affine half of GroupNorm / BatchNorm.  beta may be None.
+    Roundings: 1 forward, 1 for dx; d alpha / d beta are fp32 column reductions (mlpk_col_dot / mlpk_col_sum)."""
 
     @staticmethod
     def forward(ctx, x, alpha, beta):
+        x = _rows(x)
         with E.on_device(x):
             a32 = E.f32(alpha.reshape(-1), x.device)
             y = _ew(0, x, g=a32, h=E.f32(beta.reshape(-1), x.device) if beta is not None else None)
@@ -299,6 +348,7 @@ class Affine(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         x, a32 = ctx.saved_tensors
         dy = _rows(dy)
@@ -314,18 +364,21 @@ class Affine(torch.autograd.Function):
 
 
 class ScaleAdd(torch.autograd.Function):
-    """out = x + gamma[c] * z (res_mlp.py:53,55: x + gamma_1 * token_mix(x));  gamma None: x + z"""
+    """out = x + gamma[c] * z (res_mlp.py:53,55: x + gamma_1 * token_mix(x));  gamma None: x + z.
+    Roundings: 1 forward; dx is dy itself, dz 1 (gamma None: dy itself), d gamma an fp32 column reduction (mlpk_col_dot)."""
 
     @staticmethod
     def forward(ctx, x, z, gamma):
         with E.on_device(x):
             g32 = E.f32(gamma.reshape(-1), x.device) if gamma is not None else None
-            out = _ew(2, x, b=_rows(z), g=g32)
+            z = _rows(z)
+            out = _ew(2, _rows(x), b=z, g=g32)
         ctx.save_for_backward(z, g32)
         ctx.gshape = tuple(gamma.shape) if gamma is not None else None
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         z, g32 = ctx.saved_tensors
         dy = _rows(dy)
@@ -334,21 +387,23 @@ class ScaleAdd(torch.autograd.Function):
             if ctx.needs_input_grad[1]:
                 dz = _ew(0, dy, g=g32) if g32 is not None else dy
             if g32 is not None and ctx.needs_input_grad[2]:
-                dg = col_dot(dy, _rows(z)).reshape(ctx.gshape)
+                dg = col_dot(dy, z).reshape(ctx.gshape)
         return dy, dz, dg
 
 
 class Mul(torch.autograd.Function):
-    """out = u * v (the SGU gate, g_mlp.py:21); u, v: (M, C) rows, possibly the two halves of one wider tensor"""
+    """out = u * v (the SGU gate, g_mlp.py:21); u, v: (M, C) rows, possibly the two halves of one wider tensor.  Roundings: 1 forward, 1 per gradient."""
 
     @staticmethod
     def forward(ctx, u, v):
+        u, v = _rows(u), _rows(v)
         with E.on_device(u):
             out = _ew(1, u, b=v)
         ctx.save_for_backward(u, v)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         u, v = ctx.saved_tensors
         dy = _rows(dy)
@@ -357,16 +412,18 @@ class Mul(torch.autograd.Function):
 
 
 class RowScale(torch.autograd.Function):
-    """out[m] = x[m] * s[m // period]: stochastic depth's keep / (1 - p) per sample (as_mlp.py:159-160); s fp32, no gradient"""
+    """out[m] = x[m] * s[m // period]: stochastic depth's keep / (1 - p) per sample (as_mlp.py:159-160); s fp32, no gradient.  Roundings: 1 forward, 1 backward."""
 
     @staticmethod
     def forward(ctx, x, s, period):
+        s = s.contiguous()
         ctx.save_for_backward(s)
         ctx.period = period
         with E.on_device(x):
-            return _ew(3, x, g=s, period=period)
+            return _ew(3, _rows(x), g=s, period=period)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         (s,) = ctx.saved_tensors
         with E.on_device(dy):
@@ -374,7 +431,7 @@ class RowScale(torch.autograd.Function):
 
 
 class RowsToTokens(torch.autograd.Function):
-    """(B*C, S) rows back to token-major (B*S, C) -- RowsToTokensAdd without the residual (res_mlp.py:53: the product is scaled first)"""
+    """(B*C, S) rows back to token-major (B*S, C) -- RowsToTokensAdd without the residual (res_mlp.py:53: the product is scaled first).  Data movement both ways: no rounding."""
 
     @staticmethod
     def forward(ctx, y, B, S, C):
@@ -383,10 +440,11 @@ class RowsToTokens(torch.autograd.Function):
             return transpose(y, B, C, S, ld_out=C)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
         B, S, C = ctx.dims
         with E.on_device(dout):
-            return transpose(dout.contiguous(), B, S, C, ld_out=S), None, None, None
+            return transpose(_dense(dout), B, S, C, ld_out=S), None, None, None
 
 
 class GroupNorm1(torch.autograd.Function):
@@ -397,7 +455,7 @@ class GroupNorm1(torch.autograd.Function):
         rows, C = x.shape
         HW = rows // B
         dev = x.device
-        x = x.contiguous()
+        x = _dense(x)
         with E.on_device(x):
             mean = torch.empty((B,), dtype=torch.float32, device=dev)
             rstd = torch.empty_like(mean)
@@ -411,10 +469,11 @@ class GroupNorm1(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         xh, rstd, g32 = ctx.saved_tensors
         B, glen, gs, bs = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = dg = db = None
         with E.on_device(dy):
             if ctx.needs_input_grad[0]:
@@ -430,21 +489,23 @@ class GroupNorm1(torch.autograd.Function):
 
 
 class ShiftNHWC(torch.autograd.Function):
-    """Shift (utils/shift_cuda.py:165-192; torch_shift :177-189) on channel-last rows (B*H*W, C): the reference's one native op and its backward kernel"""
+    """Shift (utils/shift_cuda.py:165-192; torch_shift :177-189) on channel-last rows (B*H*W, C): the reference's one native op and its backward kernel.
+    x is copied unless contiguous.  Data movement both ways (zero fill outside the map): no rounding."""
 
     @staticmethod
     def forward(ctx, x, B, H, W, ksz, dim):
         ctx.meta = (B, H, W, x.shape[1], ksz, dim)
-        x = x.contiguous()
+        x = _dense(x)
         out = torch.empty_like(x)
         with E.on_device(x):
             E.shift_nhwc(x, out, B, H, W, x.shape[1], ksz, dim)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, H, W, C, ksz, dim = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = torch.empty_like(dy)
         with E.on_device(dy):
             N.check(N.lib().mlpk_shift_nhwc_backward(E.dtype_code(dy.dtype), E.ptr(dy), E.ptr(dx), B, H, W, C, ksz, dim, E.stream()), "mlpk_shift_nhwc_backward")
@@ -452,22 +513,23 @@ class ShiftNHWC(torch.autograd.Function):
 
 
 class Merge2x2(torch.autograd.Function):
-    """PatchMerging's strided gather + concatenation (as_mlp.py:207-211) on channel-last rows: (B*H*W, C) -> (B*H/2*W/2, 4C)"""
+    """PatchMerging's strided gather + concatenation (as_mlp.py:207-211) on channel-last rows: (B*H*W, C) -> (B*H/2*W/2, 4C).  Data movement both ways: no rounding."""
 
     @staticmethod
     def forward(ctx, x, B, H, W):
         C = x.shape[1]
         ctx.meta = (B, H, W, C)
-        x = x.contiguous()
+        x = _dense(x)
         out = torch.empty((B * (H // 2) * (W // 2), 4 * C), dtype=x.dtype, device=x.device)
         with E.on_device(x):
             N.check(N.lib().mlpk_merge2x2_nhwc(E.dtype_code(x.dtype), 0, E.ptr(x), E.ptr(out), B, H, W, C, E.stream()), "mlpk_merge2x2_nhwc")
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, H, W, C = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = torch.empty((B * H * W, C), dtype=dy.dtype, device=dy.device)
         with E.on_device(dy):
             N.check(N.lib().mlpk_merge2x2_nhwc(E.dtype_code(dy.dtype), 1, E.ptr(dy), E.ptr(dx), B, H, W, C, E.stream()), "mlpk_merge2x2_nhwc")
@@ -486,7 +548,7 @@ class DepthwiseConv(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, B, H, W):
         C, k = x.shape[1], w.shape[-1]
-        x = x.contiguous()
+        x = _dense(x)
         out = torch.empty_like(x)
         with E.on_device(x):
             wt = _taps(w, x.device)
@@ -497,10 +559,11 @@ class DepthwiseConv(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         x, wt = ctx.saved_tensors
         B, H, W, C, k, wshape, has_b = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = dw = db = None
         with E.on_device(dy):
             if ctx.needs_input_grad[0]:
@@ -523,6 +586,7 @@ class BatchNormTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, mean, var, eps):
         dev = x.device
+        x = _rows(x)
         with E.on_device(x):
             rs = (1.0 / torch.sqrt(var + eps)).float().contiguous()
             xh = _ew(0, x, g=rs, h=(-mean * rs.double()).float().contiguous())
@@ -532,6 +596,7 @@ class BatchNormTrain(torch.autograd.Function):
         return y
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         xh, rs, g32 = ctx.saved_tensors
         dy = _rows(dy)
@@ -553,7 +618,7 @@ class BatchNormTrain(torch.autograd.Function):
 # ---- ViP / S2-MLP: rearranges, SplitAttention, the spatial shifts (round 6) ----------------------------------------------------------------
 class VipPermute(torch.autograd.Function):
     """einops Rearrange 'b h w (c s) -> b w c (h s)' (which 0, vip.py:69) / '-> b h c (w s)' (which 1, vip.py:74) on channel-last rows:
-    (B*H*W, C) -> (B*L*G, K_pad), K = H*seg or W*seg, zero padding columns up to the GEMM's K.  Backward: the inverse rearrange."""
+    (B*H*W, C) -> (B*L*G, K_pad), K = H*seg or W*seg, zero padding columns up to the GEMM's K.  Backward: the inverse rearrange.  Data movement both ways: no rounding."""
 
     @staticmethod
     def forward(ctx, x, B, H, W, seg, which):
@@ -562,7 +627,7 @@ class VipPermute(torch.autograd.Function):
         K = (H if which == 0 else W) * seg
         kp = E.round_up(K, _epc(x.dtype))
         ctx.meta = (B, H, W, C, seg, which, kp)
-        x = x.contiguous()
+        x = _dense(x)
         z = torch.zeros((B * (W if which == 0 else H) * G, kp), dtype=x.dtype, device=x.device)
         with E.on_device(x):
             if which == 0:
@@ -572,9 +637,10 @@ class VipPermute(torch.autograd.Function):
         return z
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dz):
         B, H, W, C, seg, which, kp = ctx.meta
-        dz = dz.contiguous()
+        dz = _dense(dz)
         dx = torch.empty((B * H * W, C), dtype=dz.dtype, device=dz.device)
         with E.on_device(dz):
             E.vip_unpermute(which, dz, dx, B, H, W, C, seg, dz.stride(0))
@@ -582,21 +648,23 @@ class VipPermute(torch.autograd.Function):
 
 
 class VipUnpermute(torch.autograd.Function):
-    """the Rearrange back, 'b w c (h s) -> b h w (c s)' (which 0, vip.py:71) / 'b h c (w s) -> b h w (c s)' (which 1, vip.py:76)"""
+    """the Rearrange back, 'b w c (h s) -> b h w (c s)' (which 0, vip.py:71) / 'b h c (w s) -> b h w (c s)' (which 1, vip.py:76); columns of z behind H*seg / W*seg are padding: not read, their gradient zero.  Data movement
+    both ways: no rounding."""
 
     @staticmethod
     def forward(ctx, z, B, H, W, C, seg, which):
         ctx.meta = (B, H, W, C, seg, which, z.shape[1])
-        z = z.contiguous()
+        z = _dense(z)
         out = torch.empty((B * H * W, C), dtype=z.dtype, device=z.device)
         with E.on_device(z):
             E.vip_unpermute(which, z, out, B, H, W, C, seg, z.stride(0))
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, H, W, C, seg, which, K = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dz = torch.empty((B * (W if which == 0 else H) * (C // seg), K), dtype=dy.dtype, device=dy.device)
         with E.on_device(dy):
             if which == 0:
@@ -607,22 +675,25 @@ class VipUnpermute(torch.autograd.Function):
 
 
 class ImageSum(torch.autograd.Function):
-    """(B*S, C) -> (B, C): the sum over an image's pixels (SplitAttention's reduction, vip.py:49-50; s2_mlp_v2.py:43-44)"""
+    """(B*S, C) -> (B, C): the sum over an image's pixels (SplitAttention's reduction, vip.py:49-50; s2_mlp_v2.py:43-44).  x passes through _rows16
+    (mlpk_pool_mean: C % 8 == 0).  Roundings: 2 forward (mlpk_pool_mean stores the mean, mlpk_ew_cols the mean * S; S + 2 fp32 operations); backward:
+    data movement (dy * 1.0f)."""
 
     @staticmethod
     def forward(ctx, x, B, S):
         C = x.shape[1]
         ctx.dims = (B, S, C)
-        x = _rows(x)
+        x = _rows16(x)
         out = torch.empty((B, C), dtype=x.dtype, device=x.device)
         with E.on_device(x):
             E.pool_mean(x, B, S, C, x.stride(0), out, C)
             return _ew(0, out, g=torch.full((C,), float(S), dtype=torch.float32, device=x.device))
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, S, C = ctx.dims
-        dy = dy.contiguous()
+        dy = _dense(dy)
         dx = torch.empty((B * S, C), dtype=dy.dtype, device=dy.device)
         with E.on_device(dy):
             N.check(N.lib().mlpk_broadcast_rows(E.dtype_code(dy.dtype), E.ptr(dy), E.ptr(dx), B, S, C, 1.0, E.stream()), "mlpk_broadcast_rows")
@@ -630,11 +701,12 @@ class ImageSum(torch.autograd.Function):
 
 
 class SoftmaxBranches(torch.autograd.Function):
-    """nn.Softmax(1) over the k = 3 branches of hat_a viewed (B, 3, C) (vip.py:51-53), fp32 in and out"""
+    """nn.Softmax(1) over the k = 3 branches of hat_a viewed (B, 3, C) (vip.py:51-53), fp32 in and out.  Roundings: fp32 throughout (__expf, a sum of three, a
+    reciprocal, a product); the backward reads the forward's stored result."""
 
     @staticmethod
     def forward(ctx, hat, B, C):
-        hat = hat.contiguous()
+        hat = _dense(hat)
         bar = torch.empty_like(hat)
         with E.on_device(hat):
             E.split_softmax(hat, bar, B, C)
@@ -643,10 +715,11 @@ class SoftmaxBranches(torch.autograd.Function):
         return bar
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dbar):
         (bar,) = ctx.saved_tensors
         B, C = ctx.dims
-        dbar = dbar.contiguous()
+        dbar = _dense(dbar)
         dhat = torch.empty_like(bar)
         with E.on_device(bar):
             N.check(N.lib().mlpk_split_softmax_backward(E.ptr(bar), E.ptr(dbar), E.ptr(dhat), B, C, E.stream()), "mlpk_split_softmax_backward")
@@ -655,22 +728,25 @@ class SoftmaxBranches(torch.autograd.Function):
 
 class WeightedSum3(torch.autograd.Function):
     """out[b, n, :] = sum_k bar[b, k, :] * x_k[b, n, :] (vip.py:54-56; s2_mlp_v2.py:48-50); bar fp32 (B, 3C); the branches may be column
-    slices of one wider tensor (S2-MLPv2: the thirds of mlp1's output)"""
+    slices of one wider tensor (S2-MLPv2: the thirds of mlp1's output).  Roundings: 3 forward (three mlpk_ew_cols passes, each storing the running sum:
+    6 fp32 operations), 1 per d x_k; d bar is an fp32 reduction per image (mlpk_col_dot_seg)."""
 
     @staticmethod
     def forward(ctx, x0, x1, x2, bar, B, S):
         C = x0.shape[1]
         bar3 = bar.reshape(B, 3, C)
         parts = [bar3[:, k].contiguous() for k in range(3)]
+        x0, x1, x2 = _rows(x0), _rows(x1), _rows(x2)
         with E.on_device(x0):
-            out = _ew(5, _rows(x0), g=parts[0], period=S)
-            out = _ew(5, _rows(x1), b=out, g=parts[1], period=S)
-            out = _ew(5, _rows(x2), b=out, g=parts[2], period=S)
+            out = _ew(5, x0, g=parts[0], period=S)
+            out = _ew(5, x1, b=out, g=parts[1], period=S)
+            out = _ew(5, x2, b=out, g=parts[2], period=S)
         ctx.save_for_backward(x0, x1, x2, *parts)
         ctx.dims = (B, S, C)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         x0, x1, x2, p0, p1, p2 = ctx.saved_tensors
         B, S, C = ctx.dims
@@ -680,7 +756,6 @@ class WeightedSum3(torch.autograd.Function):
         with E.on_device(dy):
             for k, (xk, pk_) in enumerate(((x0, p0), (x1, p1), (x2, p2))):
                 grads.append(_ew(5, dy, g=pk_, period=S) if ctx.needs_input_grad[k] else None)
-                xk = _rows(xk)
                 seg = torch.empty((B, C), dtype=torch.float32, device=dy.device)
                 N.check(N.lib().mlpk_col_dot_seg(E.dtype_code(dy.dtype), E.ptr(dy), dy.stride(0), E.ptr(xk), xk.stride(0), B, S, C, E.ptr(seg), E.stream()),
                         "mlpk_col_dot_seg")
@@ -701,7 +776,8 @@ def split_attention(x0, x1, x2, sa, B, S):
 class S2Shift(torch.autograd.Function):
     """spatial_shift1 / spatial_shift2 (s2_mlp_v2.py:15-29; which 1 / 2) on (B*D1*D2, C) rows -- possibly a column slice of a wider tensor.
     Forward: the reference's in-place result (mode "reference_inplace": the +1 groups smear) or the intended shift; backward: what the
-    reference's autograd returns for the slice assignments -- the adjoint of the INTENDED shift in both modes (mlpk.h mlpk_s2_shift2)."""
+    reference's autograd returns for the slice assignments -- the adjoint of the INTENDED shift in both modes (mlpk.h mlpk_s2_shift2).  Roundings: none forward (data movement in
+    both modes), 1 backward (the border rows add two terms in fp32)."""
 
     @staticmethod
     def forward(ctx, x, B, D1, D2, which, smear):
@@ -715,6 +791,7 @@ class S2Shift(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, D1, D2, C, which = ctx.meta
         dy = _rows(dy)
@@ -726,7 +803,8 @@ class S2Shift(torch.autograd.Function):
 
 class PatchRowsNHWC(torch.autograd.Function):
     """the im2col half of Conv2d(kernel = stride = (ph, pw)) read from channel-last rows (B*H*W, C) -> (B*H/ph*W/pw, K_pad), K = ph*pw*C in
-    mlpk_patchify's NHWC order 0, zero padding columns up to the GEMM's K; backward: the inverse permutation (s2_mlp_v2.py:118-119)"""
+    mlpk_patchify's NHWC order 0, zero padding columns up to the GEMM's K; backward: the inverse permutation (s2_mlp_v2.py:118-119).  Data movement both ways:
+    no rounding."""
 
     @staticmethod
     def forward(ctx, x, B, H, W, ph, pw):
@@ -734,7 +812,7 @@ class PatchRowsNHWC(torch.autograd.Function):
         K = ph * pw * C
         kp = E.round_up(K, _epc(x.dtype))
         ctx.meta = (B, H, W, C, ph, pw, K, kp)
-        x = x.contiguous()
+        x = _dense(x)
         rows = B * (H // ph) * (W // pw)
         out = torch.empty((rows, K), dtype=x.dtype, device=x.device)
         with E.on_device(x):
@@ -742,9 +820,10 @@ class PatchRowsNHWC(torch.autograd.Function):
         return _pad_cols(out, kp)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         B, H, W, C, ph, pw, K, kp = ctx.meta
-        dy = dy[:, :K].contiguous()
+        dy = _dense(dy[:, :K])
         dx = torch.empty((B * H * W, C), dtype=dy.dtype, device=dy.device)
         with E.on_device(dy):
             N.check(N.lib().mlpk_patch_rows_nhwc(E.dtype_code(dy.dtype), 1, 0, E.ptr(dy), E.ptr(dx), B, H, W, C, ph, pw, E.stream()), "mlpk_patch_rows_nhwc")
@@ -783,26 +862,29 @@ def _index_gather(src, table, kmax, batch, n_out, n_in, width):
 
 
 class IndexMap(torch.autograd.Function):
-    """x: (B * n_in * width / cols, cols) contiguous -> (B * n_out * width / out_cols, out_cols): the remap of an IndexTable; backward: its adjoint"""
+    """x: (B * n_in * width / cols, cols) contiguous -> (B * n_out * width / out_cols, out_cols): the remap of an IndexTable; backward: its adjoint.
+    Roundings: none forward (a gather), 1 backward (the fp32 sum of up to tab.kmax readers)."""
 
     @staticmethod
     def forward(ctx, x, tab, B, out_cols):
-        x = x.contiguous()
+        x = _dense(x)
         assert x.numel() == B * tab.n_in * tab.width, (tuple(x.shape), B, tab.n_in, tab.width)
         ctx.tab, ctx.B, ctx.in_cols = tab, B, x.shape[1]
         with E.on_device(x):
             return _index_gather(x, tab.fwd, 1, B, tab.n_out, tab.n_in, tab.width).view(-1, out_cols)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         tab = ctx.tab
-        dy = dy.contiguous()
+        dy = _dense(dy)
         with E.on_device(dy):
             return _index_gather(dy, tab.inv, tab.kmax, ctx.B, tab.n_in, tab.n_out, tab.width).view(-1, ctx.in_cols), None, None, None
 
 
 class ConcatCols(torch.autograd.Function):
-    """torch.cat over the channel axis of channel-last rows (sparse_mlp.py:71, ms_mlp.py:58-59): the parts copied into column slices of one buffer"""
+    """torch.cat over the channel axis of channel-last rows (sparse_mlp.py:71, ms_mlp.py:58-59): the parts copied into column slices of one buffer.
+    Data movement both ways (the gradients are column slices of dy): no rounding."""
 
     @staticmethod
     def forward(ctx, *parts):
@@ -817,6 +899,7 @@ class ConcatCols(torch.autograd.Function):
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         outs, c0 = [], 0
         for wd in ctx.widths:
@@ -826,20 +909,22 @@ class ConcatCols(torch.autograd.Function):
 
 
 class AddPeriodic(torch.autograd.Function):
-    """x[b, l, :] + t[l, :] (SwinMLP's absolute position embedding, swin_mlp.py:437-438); t: parameter (1, L, C)"""
+    """x[b, l, :] + t[l, :] (SwinMLP's absolute position embedding, swin_mlp.py:437-438); t: parameter (1, L, C).  Roundings: 1 forward; dx is dy itself,
+    dt an fp32 column reduction over the images (mlpk_col_sum)."""
 
     @staticmethod
     def forward(ctx, x, t, L):
-        out = x.clone()
+        out = x.clone(memory_format=torch.contiguous_format)           # (a plain clone keeps a transposed view's strides: no row pitch)
         ctx.meta = (tuple(t.shape), L)
         with E.on_device(x):
             E.add_periodic(out, out.stride(0), E.f32(t, x.device), out.shape[0], out.shape[1], L)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         tshape, L = ctx.meta
-        dy = dy.contiguous()
+        dy = _dense(dy)
         Bn = dy.shape[0] // L
         with E.on_device(dy):
             dt = col_sum(dy.view(Bn, L * dy.shape[1]), Bn, L * dy.shape[1])
@@ -858,6 +943,7 @@ class Dropout(torch.autograd.Function):
         return E.dropout(x, y, x.shape[0], x.shape[1], p, seed, site)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dy):
         p, seed, site = ctx.meta
         dy = _rows(dy)

@@ -289,11 +289,21 @@ def warn_unapplied_dropout(model):
                 type(model).__name__, type(model).__name__, name, float(m.p)), RuntimeWarning, stacklevel=4)
 
 
+def warn_no_input_grad(model, x):
+    """The train paths build their patches outside autograd (autograd.conv_rows): an image that requires a gradient gets none.  A UserWarning,
+    once per model object, instead of a silent `x.grad is None` (train mode)."""
+    if x.requires_grad and not model.__dict__.get("_warned_input_grad"):
+        warnings.warn("%s.train(): the gradient with respect to the input image is not produced (parameter gradients only)" % type(model).__name__,
+                      stacklevel=5)
+        model.__dict__["_warned_input_grad"] = True
+
+
 def train_entry(model, x, warn_dropout=False):
     """The checks every `_forward_train` opens with: warn_unapplied_dropout (warn_dropout: the families whose train path applies no Dropout),
-    a GPU tensor, a (B, C, H, W) input; returns the compute dtype"""
+    warn_no_input_grad, a GPU tensor, a (B, C, H, W) input; returns the compute dtype"""
     if warn_dropout:
         warn_unapplied_dropout(model)
+    warn_no_input_grad(model, x)
     E.require_gpu(x, type(model).__name__ + ".forward")
     if x.dim() != 4:
         raise ValueError("expected a (B, C, H, W) tensor")

@@ -342,12 +342,7 @@ class MLPMixerForImageClassification(MLPMixer):
         (mlp_mixer.py:30-75; Dropout(p=0) is the identity there too).  Unfused on purpose: the pre-activations and the normalised tensors
         are what the backward needs.  The gradient w.r.t. the input image is not produced (no consumer)."""
         from .. import autograd as AG
-        cd = train_entry(self, x)
-        if x.requires_grad and not self.__dict__.get("_warned_input_grad"):
-            import warnings
-            warnings.warn("MLPMixerForImageClassification.train(): the gradient with respect to the input image is not produced "
-                          "(parameter gradients only)", stacklevel=3)
-            self.__dict__["_warned_input_grad"] = True
+        cd = train_entry(self, x)                                                                     # (warns once when x requires a gradient)
         S = self._dims[0]
         B, _, H, W = x.shape
         ph, pw = self._patch
