@@ -71,6 +71,13 @@ PITCHED = {
     "mlpk_token_mlp_ln": (("ldx",), "test_token_mlp_generated_and_ln_pitched"),
     "mlpk_as_conv2": (("ldw",), "test_as_conv2_pitched"),
     "mlpk_as_conv2_stats": (("ldw",), "test_as_conv2_pitched"),
+    "mlpk_raft_gather_ln": (("x_pitch", "a_pitch"), "test_raft_pitched"),
+    "mlpk_raft_scatter_add": (("x_pitch", "y_pitch"), "test_raft_pitched"),
+    "mlpk_atm_sample": (("x_pitch", "off_pitch", "out_pitch"), "test_atm_sample_pitched"),
+    "mlpk_dyna_mix": (("x_pitch", "t_pitch", "t_off", "out_pitch"), "test_dyna_mix_pitched"),
+    "mlpk_dyna_gather": (("t_pitch", "t_off", "v_pitch"), "test_dyna_mix_pitched"),
+    "mlpk_dyna_mix_logits": (("x_pitch", "z_pitch", "out_pitch"), "test_dyna_mix_pitched"),
+    "mlpk_lstm_scan": (("xp_pitch", "xp_off", "out_pitch", "out_off"), "test_lstm_scan_pitched"),
     "mlpk_wave_patm": (("ldy", "ldo"), "tests/test_gpu_wave.py::test_wave_patm_kernel (a sentinel in the pad columns of the output and NaN in those of the input)"),
 }
 
@@ -98,11 +105,11 @@ class Ops:
         self.items[name] = (g, zero_pad, finite)
         return g.view
 
-    def inp(self, name, data, pad=8, off=0):
-        return self._mk(name, data.shape[0], data.shape[1], data.dtype, pad, off, "in", data)
+    def inp(self, name, data, pad=8, off=0, dpad=0):
+        return self._mk(name, data.shape[0], data.shape[1], data.dtype, pad, off, "in", data, dpad=dpad)
 
-    def inout(self, name, data, pad=8, off=0):
-        return self._mk(name, data.shape[0], data.shape[1], data.dtype, pad, off, "inout", data)
+    def inout(self, name, data, pad=8, off=0, dpad=0):
+        return self._mk(name, data.shape[0], data.shape[1], data.dtype, pad, off, "inout", data, dpad=dpad)
 
     def out(self, name, rows, cols, dtype, pad=8, off=0, zero_pad=False, finite=True, dpad=0):
         return self._mk(name, rows, cols, dtype, pad, off, "out", zero_pad=zero_pad, finite=finite, dpad=dpad)
@@ -1449,3 +1456,243 @@ def test_swin_spatial_guarded(dtype):
                            out_stats=(ops.vec("out_mean", rows), ops.vec("out_rstd", rows)))
             return lambda ops: assert_bits_equal(ops.g("x_stats").dense(), ops.g("x").dense(), "x with and without statistics")
         one(case)
+
+
+# ------------------------------------------------------------------ the *_pitch / *_off families: RaftMLP, ActiveMLP, DynaMixer, Sequencer2D
+# Their headers demand 16-byte bases and pitches for the vector operands and say "the results do not depend on the pitches": (c) always holds.
+def per16(dtype):
+    """elements per 16 bytes"""
+    return 4 if dtype == torch.float32 else 8
+
+
+def aligned_leads(dtype):
+    """the lead offsets (of guard.LEAD_OFFSETS) that keep a base on a 16-byte boundary: 4 elements only in fp32"""
+    return (0, 4) if dtype == torch.float32 else (0,)
+
+
+def restride(v, ld, shift=0):
+    """the 2-d view v at another row pitch and `shift` elements further on (for the refusals: nothing is read or written through it)"""
+    return torch.as_strided(v, tuple(v.shape), (ld, 1), v.storage_offset() + shift)
+
+
+def wide(rows, cols, dtype, extra):
+    """a (rows, cols) view of a zero buffer with `extra` spare columns behind every row"""
+    return torch.zeros((rows, cols + extra), dtype=dtype, device=DEV)[:, :cols]
+
+
+def ln_operands(x, C, seed):
+    mean, rstd = row_ln(x)
+    return mean, rstd, rd((C,), torch.float32, seed) * 0.3 + 1, rd((C,), torch.float32, seed + 1) * 0.2
+
+
+@pytest.mark.parametrize("axis", [0, 1], ids=["vertical", "horizontal"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=[IDS[d] for d in DTYPES])
+def test_raft_pitched(dtype, axis):
+    """mlpk_raft_gather_ln and mlpk_raft_scatter_add on a 5 x 3 map of 16 channels, r = 2, three images: x at C + e, a at kp + 2e (columns [D, kp)
+    exactly +0, [kp, a_pitch) poison), y at the first aligned pitch beyond D + e with NaN behind column D, x updated in place inside its bands;
+    every 16-byte lead the type has"""
+    E, N = pk()
+    B_, H, W, C, r = 3, 5, 3, 16, 2
+    assert E.raft_supported(dtype, H, W, C, r, axis)
+    e = per16(dtype)
+    L, Q = (H, W) if axis == 0 else (W, H)
+    Co, D, rows = C // r, r * L, B_ * H * W
+    items, kp = B_ * Q * Co, E.round_up(D + 1, e)
+    dy = E.round_up(D, e) - D                                  # what the dense twin of y needs for a 16-byte pitch
+    x, y = rd((rows, C), dtype, 1 + axis) + 0.25, rd((items, D), dtype, 3 + axis)
+    mean, rstd, gamma, beta = ln_operands(x, C, 5)
+    for lead in aligned_leads(dtype):
+        def case(ops):
+            a = ops.out("a", items, kp, dtype, pad=2 * e, off=lead)
+            E.raft_gather_ln(ops.inp("x", x, pad=e, off=lead), mean, rstd, gamma, beta, a, kp, B_, H, W, C, r, axis)
+            E.raft_scatter_add(ops.inout("xs", x, pad=e, off=lead), ops.inp("y", y, pad=dy + e, off=lead, dpad=dy), B_, H, W, C, r, axis)
+
+            def post(ops):
+                pad0 = ops.g("a").view[:, D:kp].contiguous().view(torch.int32 if dtype == torch.float32 else torch.int16)
+                assert kp > D and int((pad0 != 0).sum()) == 0, "columns [D, kp) of a are not +0"
+                assert not torch.equal(ops.g("xs").dense(), x), "nothing was added"
+            return post
+        both(case)
+    ga, gx = Guarded(items, kp, kp + e, dtype, DEV), Guarded(rows, C, C + e, dtype, DEV)
+    xw, yw = wide(rows, C, dtype, e), wide(items, D, dtype, dy + e)
+    gather = lambda xv, av, k=kp: (lambda: E.raft_gather_ln(xv, mean, rstd, gamma, beta, av, k, B_, H, W, C, r, axis))
+    scatter = lambda xv, yv: (lambda: E.raft_scatter_add(xv, yv, B_, H, W, C, r, axis))
+    refused(N, gather(restride(xw, C - e), ga.view), ga)                        # x_pitch < C
+    refused(N, gather(restride(xw, C + e // 2), ga.view), ga)                   # x_pitch off the 16-byte grid
+    refused(N, gather(restride(xw, C + e, e // 2), ga.view), ga)                # x 8 bytes off
+    refused(N, gather(xw, ga.view, kp + 2 * e), ga)                             # kp beyond a_pitch
+    refused(N, gather(xw, restride(ga.view, kp - e)), ga)                       # a_pitch < kp
+    refused(N, gather(xw, restride(ga.view, kp + e, e // 2)), ga)               # a 8 bytes off
+    refused(N, scatter(restride(gx.view, C - e), yw), gx)                       # x_pitch < C
+    refused(N, scatter(restride(gx.view, C + e, e // 2), yw), gx)               # x 8 bytes off
+    refused(N, scatter(gx.view, restride(yw, D // e * e if D % e else D - e)), gx)      # y_pitch < D
+    refused(N, scatter(gx.view, restride(yw, D + dy + e // 2)), gx)             # y_pitch off the 16-byte grid
+    refused(N, scatter(gx.view, restride(yw, D + dy + e, e // 2)), gx)          # y 8 bytes off
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=[IDS[d] for d in DTYPES])
+def test_atm_sample_pitched(dtype):
+    """mlpk_atm_sample on a 5 x 7 map of 16 channels, share 2, three images: the three outputs as column slices of one (rows, 3C) buffer at
+    3C + e, then out_w and out_c alone with a gap between them that must stay poison; `off` needs element alignment only: an odd lead and an
+    odd pitch, NaN behind its 2C / share columns"""
+    E, N = pk()
+    B_, H, W, C, share = 3, 5, 7, 16, 2
+    assert E.atm_sample_supported(dtype, H, W, C, share)
+    e, rows, oc = per16(dtype), B_ * H * W, 2 * C // share
+    x = rd((rows, C), dtype, 1) + 0.25
+    off = rd((rows, oc), dtype, 2, 1.5)                         # positions inside, between and beyond the pixels of a line
+    mean, rstd, gamma, beta = ln_operands(x, C, 3)
+    for lead in aligned_leads(dtype):
+        def case(ops):
+            o = ops.out("out", rows, 3 * C, dtype, pad=e, off=lead)
+            E.atm_sample(ops.inp("x", x, pad=e, off=lead), mean, rstd, gamma, beta, ops.inp("off", off, pad=3, off=1), share,
+                         o[:, :C], o[:, C:2 * C], o[:, 2 * C:], B_, H, W, C)
+            g = ops.out("gap", rows, 2 * C + e, dtype, pad=2 * e, off=lead, finite=False)
+            E.atm_sample(ops.inp("x2", x, pad=2 * e, off=lead), mean, rstd, gamma, beta, ops.inp("off2", off, pad=1, off=1), share,
+                         g[:, :C], None, g[:, C + e:], B_, H, W, C)
+
+            def post(ops):
+                gg, oo = ops.g("gap"), ops.g("out").view
+                gg.still_poison(C, C + e)
+                assert_bits_equal(gg.view[:, :C].contiguous(), oo[:, :C].contiguous(), "out_w without out_h")
+                assert_bits_equal(gg.view[:, C + e:].contiguous(), oo[:, 2 * C:].contiguous(), "out_c without out_h")
+                assert not torch.equal(oo[:, :C], oo[:, 2 * C:]) and not torch.equal(oo[:, C:2 * C], oo[:, 2 * C:]), "the offsets moved nothing"
+            return post
+        both(case)
+    go = Guarded(rows, 3 * C, 3 * C + e, dtype, DEV)
+    xw, ow = wide(rows, C, dtype, e), wide(rows, oc, dtype, 3)
+    ov = go.view
+    call = lambda xv, fv, o3: (lambda: E.atm_sample(xv, mean, rstd, gamma, beta, fv, share, o3[0], o3[1], o3[2], B_, H, W, C))
+    slices = lambda v: (v[:, :C], v[:, C:2 * C], v[:, 2 * C:])
+    refused(N, call(restride(xw, C - e), ow, slices(ov)), go)                                   # x_pitch < C
+    refused(N, call(restride(xw, C + e // 2), ow, slices(ov)), go)                              # x_pitch off the 16-byte grid
+    refused(N, call(restride(xw, C + e, e // 2), ow, slices(ov)), go)                           # x 8 bytes off
+    refused(N, call(xw, restride(ow, oc - 1), slices(ov)), go)                                  # off_pitch < 2C / share
+    refused(N, call(xw, ow, (restride(ov[:, :C], C - e), None, None)), go)                      # out_pitch < C
+    refused(N, call(xw, ow, (restride(ov[:, :C], 3 * C + e // 2), None, None)), go)             # out_pitch off the 16-byte grid
+    refused(N, call(xw, ow, tuple(restride(v, 3 * C + e, e // 2) for v in slices(ov))), go)     # the outputs 8 bytes off
+    refused(N, call(xw, ow, (ov[:, :C], restride(ov[:, C:2 * C], 3 * C + e, e // 2), ov[:, 2 * C:])), go)      # one of them
+
+
+@pytest.mark.parametrize("form", ["fused", "unfused"])
+@pytest.mark.parametrize("dtype", DTYPES, ids=[IDS[d] for d in DTYPES])
+def test_dyna_mix_pitched(dtype, form):
+    """mlpk_dyna_mix (fused) and mlpk_dyna_gather + mlpk_dyna_mix_logits (unfused) on a 5 x 3 map of 24 channels, s = 3, hd = 2, three images:
+    both axes read ONE t (rows, 2 s hd) at t_off = 0 and s hd and write the two column blocks of ONE (rows, 2C) buffer.  t, v and z need element
+    alignment only: odd leads and odd pitches."""
+    E, N = pk()
+    B_, H, W, C, s, hd = 3, 5, 3, 24, 3, 2
+    e, rows, nt = per16(dtype), B_ * H * W, s * hd
+    x = rd((rows, C), dtype, 1) + 0.25
+    t = rd((rows, 2 * nt), dtype, 2, 2.0)
+    mean, rstd, gamma, beta = ln_operands(x, C, 3)
+    geo, aw, ab, z = {}, {}, {}, {}
+    for axis in (0, 1):
+        L, Q = (H, W) if axis == 0 else (W, H)
+        assert E.dyna_mix_supported(dtype, L, C, s, hd)
+        K, nn, items = L * hd, L * L, B_ * Q * s
+        kp = E.round_up(K + 1, 8)
+        geo[axis] = (L, K, nn, items, kp)
+        A, b = rnd((nn, K), torch.float32, 10 + axis, 0.7), rnd((nn,), torch.float32, 12 + axis)
+        if form == "fused":
+            aw[axis], ab[axis] = E.pack_dyna_attend(A, b, dtype, torch.device(DEV))
+        else:                                                   # the logits of the unfused form, once: torch's Linear on the gathered rows
+            v = torch.empty((items, kp), dtype=dtype, device=DEV)
+            E.dyna_gather(t, axis * nt, v, kp, B_, H, W, s, hd, axis)
+            sync()
+            z[axis] = torch.nn.functional.linear(v[:, :K].contiguous(), A.to(DEV).to(dtype), b.to(DEV).to(dtype))
+            assert_finite(z[axis], "logits")
+    for lead in aligned_leads(dtype):
+        def case(ops):
+            xv, tv = ops.inp("x", x, pad=e, off=lead), ops.inp("t", t, pad=3, off=1)
+            o = ops.out("out", rows, 2 * C, dtype, pad=e, off=lead)
+            for axis in (0, 1):
+                L, K, nn, items, kp = geo[axis]
+                ob = o[:, axis * C:(axis + 1) * C]
+                if form == "fused":
+                    E.dyna_mix(xv, mean, rstd, gamma, beta, tv, axis * nt, aw[axis], ab[axis], ob, B_, H, W, C, s, hd, axis)
+                else:
+                    E.dyna_gather(tv, axis * nt, ops.out("v%d" % axis, items, kp, dtype, pad=3, off=1), kp, B_, H, W, s, hd, axis)
+                    E.dyna_mix_logits(xv, mean, rstd, gamma, beta, ops.inp("z%d" % axis, z[axis], pad=5, off=1), ob, B_, H, W, C, s, hd, axis)
+                if axis == 0:
+                    sync()
+                    ops.g("out").still_poison(C, 2 * C)         # the other axis's block
+
+            def post(ops):
+                oo = ops.g("out").view
+                assert not torch.equal(oo[:, :C], oo[:, C:]), "the two axes gave one result"
+                for axis in (0, 1) if form == "unfused" else ():
+                    L, K, nn, items, kp = geo[axis]
+                    pad0 = ops.g("v%d" % axis).view[:, K:].contiguous().view(torch.int32 if dtype == torch.float32 else torch.int16)
+                    assert kp > K and int((pad0 != 0).sum()) == 0, "columns [L hd, kp) of v are not +0"
+            return post
+        both(case)
+    go = Guarded(rows, 2 * C, 2 * C + e, dtype, DEV)
+    xw, tw = wide(rows, C, dtype, e), wide(rows, 2 * nt, dtype, 3)
+    ob, axis = go.view[:, C:], 1
+    L, K, nn, items, kp = geo[axis]
+    if form == "fused":
+        call = lambda xv, tv, ov, toff=nt: (lambda: E.dyna_mix(xv, mean, rstd, gamma, beta, tv, toff, aw[axis], ab[axis], ov, B_, H, W, C, s, hd, axis))
+        refused(N, call(xw, restride(tw, 2 * nt - 1), ob), go)                  # t_pitch < t_off + s hd
+        refused(N, call(xw, tw, ob, -1), go)                                    # t_off < 0
+    else:
+        gv, zw = Guarded(items, kp, kp + 3, dtype, DEV), wide(items, nn, dtype, 5)
+        gather = lambda tv, vv, toff=nt, k=kp: (lambda: E.dyna_gather(tv, toff, vv, k, B_, H, W, s, hd, axis))
+        refused(N, gather(restride(tw, 2 * nt - 1), gv.view), gv)               # t_pitch < t_off + s hd
+        refused(N, gather(tw, gv.view, -1), gv)                                 # t_off < 0
+        refused(N, gather(tw, restride(gv.view, kp - 1)), gv)                   # v_pitch < kp
+        refused(N, gather(tw, gv.view, nt, K - 1), gv)                          # kp < L hd
+        call = lambda xv, zv, ov: (lambda: E.dyna_mix_logits(xv, mean, rstd, gamma, beta, zv, ov, B_, H, W, C, s, hd, axis))
+        refused(N, call(xw, restride(zw, nn - 1), ob), go)                      # z_pitch < L L
+        tw = zw                                                                 # (the second operand of `call` in this form)
+    refused(N, call(restride(xw, C - e), tw, ob), go)                           # x_pitch < C
+    refused(N, call(restride(xw, C + e // 2), tw, ob), go)                      # x_pitch off the 16-byte grid
+    refused(N, call(restride(xw, C + e, e // 2), tw, ob), go)                   # x 8 bytes off
+    refused(N, call(xw, tw, restride(ob, C - e)), go)                           # out_pitch < C
+    refused(N, call(xw, tw, restride(ob, 2 * C + e // 2)), go)                  # out_pitch off the 16-byte grid
+    refused(N, call(xw, tw, restride(ob, 2 * C + e, e // 2)), go)               # out 8 bytes off
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=[IDS[d] for d in DTYPES])
+def test_lstm_scan_pitched(dtype):
+    """mlpk_lstm_scan on a 5 x 3 map, hid 16, two and three images (6 / 10 and 9 / 15 sequences): both axes read ONE xp (rows, 16 hid) at
+    xp_off = 0 and 8 hid and write the two halves of ONE block buffer (rows, 4 hid) through out_off = 0 and 2 hid.  Pitches of width + 4 (rows
+    on 8-byte boundaries only in the 16-bit types) and + 12"""
+    E, N = pk()
+    H, W, hid = 5, 3, 16
+    e = per16(dtype)
+    pw = [E.pack_lstm_hh(rnd((4 * hid, hid), torch.float32, 3 + a, 0.5), rnd((4 * hid, hid), torch.float32, 5 + a, 0.5), dtype, torch.device(DEV)) for a in (0, 1)]
+    for B_ in (2, 3):
+        rows = B_ * H * W
+        xp = rd((rows, 16 * hid), dtype, B_)
+        for lead in aligned_leads(dtype):
+            for pad in (4, 12):
+                def case(ops):
+                    xv = ops.inp("xp", xp, pad=pad, off=lead)
+                    o = ops.out("out", rows, 4 * hid, dtype, pad=pad, off=lead)
+                    E.lstm_scan(xv, 0, pw[0], o, 0, B_, H, W, hid, 0)
+                    sync()
+                    ops.g("out").still_poison(2 * hid, 4 * hid)                 # the other axis's half
+                    E.lstm_scan(xv, 8 * hid, pw[1], o, 2 * hid, B_, H, W, hid, 1)
+
+                    def post(ops):
+                        oo = ops.g("out").view
+                        assert not torch.equal(oo[:, :2 * hid], oo[:, 2 * hid:]), "the two axes gave one result"
+                    return post
+                both(case)
+    go = Guarded(rows, 4 * hid, 4 * hid + 4, dtype, DEV)
+    xw = wide(rows, 16 * hid, dtype, 8)
+    call = lambda xv, xoff, ov, ooff: (lambda: E.lstm_scan(xv, xoff, pw[1], ov, ooff, B_, H, W, hid, 1))
+    refused(N, call(restride(xw, 16 * hid - 4), 8 * hid, go.view, 2 * hid), go)                 # xp_pitch < xp_off + 8 hid
+    refused(N, call(xw, 8 * hid + 12, go.view, 2 * hid), go)                                    # ... by the offset (xw's own pitch is 16 hid + 8)
+    refused(N, call(xw, 8 * hid, restride(go.view, 4 * hid - 4), 2 * hid), go)                  # out_pitch < out_off + 2 hid
+    refused(N, call(xw, 8 * hid, go.view, 2 * hid + 8), go)                                     # ... by the offset
+    refused(N, call(xw, -4, go.view, 0), go)                                                    # a negative offset
+    refused(N, call(restride(xw, 16 * hid + 8), 2, go.view, 0), go)                             # xp_off no multiple of 4
+    refused(N, call(xw, 0, go.view, 2), go)                                                     # out_off no multiple of 4
+    refused(N, call(restride(xw, 16 * hid + 2), 0, go.view, 0), go)                             # xp_pitch no multiple of 4
+    refused(N, call(xw, 0, restride(go.view, 4 * hid + 2), 0), go)                              # out_pitch no multiple of 4
+    refused(N, call(restride(xw, 16 * hid + 8, e // 2), 0, go.view, 0), go)                     # xp 8 bytes off
+    refused(N, call(xw, 0, restride(go.view, 4 * hid + 4, e // 2), 0), go)                      # out 8 bytes off
+    gb = Guarded(rows, 10 * hid, 10 * hid + 4, dtype, DEV)                                      # xp and out as column blocks of ONE buffer:
+    refused(N, call(gb.view, 0, gb.view, 8 * hid), gb)                                          # the span read overlaps the span written

@@ -1,7 +1,7 @@
 """-m gpu: Sequencer2D on the MI355X.
   * mlpk_lstm_scan alone, behind guard bands (tests/guard.py), both axes, three dtypes, dense operands and operands pitched with nonzero column
-    offsets.  SHAPES (B, H, W, hid) cover L = 1, short and odd lines, fewer sequences than a tile, a tail tile, every required hid and the
-    model's two line lengths (32 and 16).
+    offsets.  SHAPES (B, H, W, hid) cover L = 1, short and odd lines, fewer sequences than a tile, a tail tile, every required hid, the
+    model's two line lengths (32 and 16) and, for every hid, a tail workgroup behind a full one whose second 16-sequence tile is partly live.
       value -- against a restatement: fp64 torch.nn.LSTM on the CPU on the STORED operands (the projections enter through an identity weight_ih).
       The gate is measured against torch itself: d(dtype) = the distance of the CPU nn.LSTM run in that type from the fp64 one on the same case;
       gate = 4 d in fp32 (another summation order over K <= 96 and the hardware's exp against libm swing a handful of ulps), 2 d in the 16-bit
@@ -10,7 +10,11 @@
       structure, as equalities -- (a) weight_hh = 0 and the forget gate at -200: the scan equals the same kernel on B H W sequences of length 1;
       (b) the map flipped along the axis with the directions' weights and xp blocks swapped gives the flipped output with the blocks swapped;
       (c) the axis-0 scan equals the axis-1 scan of the transposed map; (d) a NaN in one sequence changes no bit of another; (e) pre-activations
-      of +-1e4 stay finite and inside the value gate; (f) two runs agree.
+      of +-1e4 stay finite and inside the value gate; (f) two runs agree; (g) every sequence of a map of identical lines has sequence 0's bits.
+      the recurrence, bit for bit -- W_hh one-hot (+-1 at column pi(j) of row j of one gate) and the forget gate at -200: the scan equals one more
+      launch of single steps whose fed gate is built from the scan's own output (tests/lstm_model.py; tests/test_sequencer_host.py holds the
+      checks against planted faults).  The forget gate, which no single step replays, takes the same rows against fp64 nn.LSTM under the value
+      rule, the gate at most a fifth of the distance to the identity permutation;
       size -- a 1100 x 1024 map whose rows end past element 2^31 of both buffers equals the kernel on a dense copy of its last sequences.
   * the family against tests/golden/sequencer.npz (the reference's own forwards, tests/golden/make_sequencer_golden.py): fp32 at
     1e-5 max(1, max|ref|), the 16-bit types at twice the reference's own distance in that type on the same case.
@@ -26,6 +30,8 @@ import torch
 
 from conftest import GOLDEN, load_pkg
 from guard import Guarded, assert_bits_equal, assert_finite
+import lstm_model as LM
+from lstm_model import from_seqs, random_operands as operands, restate, to_seqs
 from oracle.portable_init import portable_input, portable_state_dict, portable_tensor
 import test_lifecycle_host as LH
 
@@ -35,7 +41,11 @@ FIX = os.path.join(GOLDEN, "sequencer.npz")
 SQ = load_pkg().models_pytorch.sequencer
 DTYPES = [torch.float32, torch.float16, torch.bfloat16]
 IDS = ["fp32", "fp16", "bf16"]
-SHAPES = [(2, 5, 3, 16), (1, 1, 7, 16), (3, 4, 37, 32), (2, 32, 6, 48), (2, 16, 5, 96)]
+HIDS = [16, 32, 48, 96]
+# (1, 51, 3): along axis 1, 51 sequences of length 3 -- a full workgroup and a tail whose second 16-sequence tile is partly live in the 16-bit
+# types (three full workgroups and three sequences in fp32); along axis 0, three sequences of length 51
+MASK_MAP = (1, 51, 3)
+SHAPES = [(2, 5, 3, 16), (1, 1, 7, 16), (3, 4, 37, 32), (2, 32, 6, 48), (2, 16, 5, 96)] + [MASK_MAP + (hid,) for hid in HIDS]
 NAME = "sequencer2d"
 
 
@@ -60,15 +70,6 @@ AXES = pytest.mark.parametrize("axis", [0, 1], ids=["v", "h"])
 PADS = pytest.mark.parametrize("pad", [0, 1], ids=["dense", "pitched"])
 
 
-def operands(B, H, W, hid, dtype, seed, hh_scale=2.0):
-    """xp (rows, 8 hid) standard normal and whh (2, 4 hid, hid) drawn like nn.LSTM's default init (U(+-1 / sqrt hid)) times hh_scale, both as
-    the storage type holds them, in fp32 on the CPU"""
-    g = torch.Generator().manual_seed(seed)
-    xp = torch.randn((B * H * W, 8 * hid), generator=g).to(dtype).float()
-    whh = ((torch.rand((2, 4 * hid, hid), generator=g) * 2 - 1) * hid ** -0.5 * hh_scale).to(dtype).float()
-    return xp, whh
-
-
 def run_scan(xp, whh, B, H, W, hid, dtype, axis, pad=0):
     """the kernel on xp (rows, 8 hid) and whh (2, 4 hid, hid), CPU fp32 tensors holding storage-type values -> (rows, 2 hid) in `dtype` on the CPU.
     pad: xp sits at column offset 8 of a wider buffer whose other columns are NaN, at a pitch beyond its width; the output is columns
@@ -89,34 +90,6 @@ def run_scan(xp, whh, B, H, W, hid, dtype, axis, pad=0):
     go.still_poison(0, ooff)
     go.still_poison(ooff + 2 * hid, ocols)
     return go.view[:, ooff:ooff + 2 * hid].clone().contiguous().cpu()
-
-
-def to_seqs(v, B, H, W, axis):
-    """(B H W, n) rows of the map -> (sequences, L, n): the reference's reshapes (sequencer.py:40, :42)"""
-    v = v.reshape(B, H, W, -1)
-    return v.permute(0, 2, 1, 3).reshape(B * W, H, -1) if axis == 0 else v.reshape(B * H, W, -1)
-
-
-def from_seqs(o, B, H, W, axis):
-    """(sequences, L, n) -> (B H W, n) (sequencer.py:41, :43)"""
-    o = o.reshape(B, W, H, -1).permute(0, 2, 1, 3) if axis == 0 else o.reshape(B, H, W, -1)
-    return o.reshape(B * H * W, -1)
-
-
-def restate(xp, whh, B, H, W, hid, axis, dtype):
-    """torch.nn.LSTM(bidirectional, batch_first) on the CPU in `dtype`: the projections xp enter through weight_ih = [I | 0] (forward) and
-    [0 | I] (reverse) with zero biases, so W_ih x + b is xp's own block exactly, in every type"""
-    rnn = torch.nn.LSTM(8 * hid, hid, num_layers=1, batch_first=True, bias=True, bidirectional=True)
-    eye, zero = torch.eye(4 * hid), torch.zeros(4 * hid, 4 * hid)
-    with torch.no_grad():
-        rnn.weight_ih_l0.copy_(torch.cat([eye, zero], 1))
-        rnn.weight_ih_l0_reverse.copy_(torch.cat([zero, eye], 1))
-        rnn.weight_hh_l0.copy_(whh[0])
-        rnn.weight_hh_l0_reverse.copy_(whh[1])
-        for n in ("bias_ih_l0", "bias_hh_l0", "bias_ih_l0_reverse", "bias_hh_l0_reverse"):
-            getattr(rnn, n).zero_()
-        out, _ = rnn.to(dtype)(to_seqs(xp, B, H, W, axis).to(dtype))
-    return from_seqs(out, B, H, W, axis).double()
 
 
 def value_case(what, xp, whh, B, H, W, hid, dtype, axis, pad):
@@ -232,6 +205,43 @@ def test_two_runs_agree(B, H, W, hid, dtype, axis):
     """(f)"""
     xp, whh = operands(B, H, W, hid, dtype, B * 1000 + H * 100 + W * 10 + hid + axis + 240)
     assert_bits_equal(run_scan(xp, whh, B, H, W, hid, dtype, axis, 1), run_scan(xp, whh, B, H, W, hid, dtype, axis, 1), "the second run")
+
+
+# ------------------------------------------------------------------ the recurrence itself (tests/lstm_model.py)
+def gpu_scan(xp, whh, B, H, W, hid, dtype, axis):
+    return run_scan(xp, whh, B, H, W, hid, dtype, axis, 1)
+
+
+ON_MASK_MAP = pytest.mark.parametrize("hid,dtype", [pytest.param(hid, dtype, id="hid%d-%s" % (hid, name)) for hid in HIDS for dtype, name in zip(DTYPES, IDS)])
+
+
+@ON_MASK_MAP
+@AXES
+@pytest.mark.parametrize("gate", ["i", "g", "o"])
+def test_one_hot_recurrence_replays_bit_for_bit(hid, dtype, axis, gate):
+    """W_hh[d] zero but for +-1 at column pi_d(j) of row j of `gate`, f at -200: z of the fed gate is +-h_{t-1}[pi(j)] exactly, so the scan
+    must equal one launch of B H W single steps fed with the scan's own output at the previous pixel.  A k slot exchanged, a wave on another
+    wave's rows, the other direction's weights or a stale h buffer move bits here; no tolerance."""
+    for kind in LM.KINDS:
+        fed = LM.replay_check(gpu_scan, *MASK_MAP, hid, dtype, axis, gate, kind)
+        assert fed > 0, "no recurrent term was fed: the case checks nothing"
+
+
+@ON_MASK_MAP
+@AXES
+def test_one_hot_forget_gate_against_fp64_lstm(hid, dtype, axis):
+    """the same one-hot rows in the forget gate, f's xp random: c_{-1} = 0 keeps a single step from replaying it, so the fp64 restatement under
+    the value rule (4 d in fp32, 2 d in the 16-bit types), the gate at most a fifth of the distance to pi = identity (both CPU figures, held
+    in tests/test_sequencer_host.py as well)"""
+    for kind in LM.KINDS:
+        LM.forget_check(gpu_scan, *MASK_MAP, hid, dtype, axis, kind)
+
+
+@ON_MASK_MAP
+@AXES
+def test_identical_sequences_give_identical_bits(hid, dtype, axis):
+    """(g) the header's sentence that the results do not depend on where in the map (in which workgroup and lane) a sequence lies"""
+    LM.identical_check(gpu_scan, *MASK_MAP, hid, dtype, axis)
 
 
 @AXES

@@ -4,6 +4,7 @@ Fake "kernels" -- plain torch functions on CPU `Guarded` buffers -- each break t
 assertion must catch every one, and pass a correct fake.  The gate parses include/mlpk.h: every entry point (and descriptor) with a pitch or stride
 parameter is either in the PITCHED table that names its GPU test or in EXEMPT with a reason, so a future entry point with a pitch fails here until
 it is covered."""
+import ast
 import os
 import re
 
@@ -184,7 +185,9 @@ def test_bands_are_a_pitch_row_and_2048_elements_at_least():
 
 
 # ------------------------------------------------------------------ the coverage gate
-PITCH_NAME = re.compile(r"^(ld|ld[a-z0-9]{1,2}|ld_\w+|\w+_ld|src_px_stride|plane_stride)$")      # (not lds_bytes)
+# ld*, *_ld and the two strides; *_pitch; and *_off, a column offset, which relocates an operand inside its row exactly as a pitch does
+# (not lds_bytes, and not the POINTER `off` of mlpk_atm_sample)
+PITCH_NAME = re.compile(r"^(ld|ld[a-z0-9]{1,2}|ld_\w+|\w+_ld|src_px_stride|plane_stride|\w+_pitch|\w+_off)$")
 
 # entry point (or "entry.parameter") -> why no guarded call covers it
 EXEMPT = {
@@ -224,8 +227,13 @@ def test_the_header_parser_sees_the_pitches():
     assert found["mlpk_transpose_batched"] == {"ld_in", "ld_out", "ld_res"}
     assert found["mlpk_patchify"] == {"src_px_stride", "ldo"}
     assert found["mlpk_mixshift_nhwc_stats"] == {"row_part_ld"}
+    assert found["mlpk_lstm_scan"] == {"xp_pitch", "xp_off", "out_pitch", "out_off"}
+    assert found["mlpk_dyna_mix"] == {"x_pitch", "t_pitch", "t_off", "out_pitch"}
+    assert found["mlpk_atm_sample"] == {"x_pitch", "off_pitch", "out_pitch"}                   # (`off` itself is a pointer)
+    assert found["mlpk_raft_gather_ln"] == {"x_pitch", "a_pitch"}
+    assert PITCH_NAME.match("v_pitch") and PITCH_NAME.match("out_off") and not PITCH_NAME.match("off") and not PITCH_NAME.match("lds_bytes")
     assert "mlpk_split_softmax" not in found and "mlpk_convert" not in found
-    assert len(found) >= 45 and "mlpk_gemm_algo_info" not in found
+    assert len(found) >= 52 and "mlpk_gemm_algo_info" not in found                             # (45 before the *_pitch / *_off entry points)
 
 
 def test_every_pitched_entry_point_is_covered_or_exempt():
@@ -247,8 +255,18 @@ def test_every_pitched_entry_point_is_covered_or_exempt():
 
 
 def test_the_table_names_tests_that_exist():
+    """a bare name is a function of tests/test_gpu_pitched.py; tests/<file>.py::<name> is looked up in that file's syntax tree (the GPU files
+    build models at import: they are parsed, not imported)"""
     import test_gpu_pitched
     for name, (_, tests) in PITCHED.items():
         for t in tests.split(", "):
             if not t.startswith("tests/"):
                 assert callable(getattr(test_gpu_pitched, t, None)), (name, t)
+                continue
+            m = re.match(r"^tests/(\w+\.py)::(\w+)\b", t)
+            assert m, (name, t)
+            path = os.path.join(ROOT, "tests", m.group(1))
+            assert os.path.isfile(path), (name, t)
+            with open(path) as f:
+                tree = ast.parse(f.read(), path)
+            assert any(isinstance(n, ast.FunctionDef) and n.name == m.group(2) for n in tree.body), (name, t)

@@ -16,7 +16,8 @@ from torch import nn
 
 from conftest import GOLDEN, ROOT, load_pkg
 import test_lifecycle_host as LH
-from test_gpu_sequencer import NAME, SHAPES, add_tiny_settings, from_seqs, sequencer_config, to_seqs
+import lstm_model as LM
+from test_gpu_sequencer import DTYPES, HIDS, IDS, MASK_MAP, NAME, SHAPES, add_tiny_settings, from_seqs, operands, restate, sequencer_config, to_seqs
 
 FIX = os.path.join(GOLDEN, "sequencer.npz")
 SQ = load_pkg().models_pytorch.sequencer
@@ -240,6 +241,94 @@ def test_layernorm_fold_of_the_projection():
     alone = {}
     SQ.pack_bilstm(alone, "", mod, None, torch.bfloat16, torch.device("cpu"))
     assert "ih.csum" not in alone and alone["ih.w"].dtype == torch.bfloat16 and alone["ih.b"].dtype == torch.float32
+
+
+# ------------------------------------------------------------------ the CPU model of the scan (tests/lstm_model.py) and its planted faults
+MODEL_CASES = pytest.mark.parametrize("hid,dtype", [pytest.param(hid, dtype, id="hid%d-%s" % (hid, name)) for hid in HIDS for dtype, name in zip(DTYPES, IDS)])
+AXES = pytest.mark.parametrize("axis", [0, 1], ids=["v", "h"])
+
+
+def model(fault=None):
+    return lambda xp, whh, B, H, W, hid, dtype, axis: LM.scan_model(xp, whh, B, H, W, hid, dtype, axis, fault)
+
+
+@pytest.mark.parametrize("hid", HIDS)
+@AXES
+def test_the_model_equals_fp64_lstm_within_the_fp32_gate(hid, axis):
+    """the faultless model in fp32 storage against fp64 nn.LSTM on random operands: 4 d, d = the distance of torch's own fp32 LSTM (the rule of
+    tests/test_gpu_sequencer.py), at most a fifth of the distance to the restatement without the recurrence"""
+    for B, H, W in (MASK_MAP, (2, 5, 3)):
+        xp, whh = operands(B, H, W, hid, torch.float32, 100 * hid + axis)
+        exact = restate(xp, whh, B, H, W, hid, axis, torch.float64)
+        gate = 4.0 * float((restate(xp, whh, B, H, W, hid, axis, torch.float32) - exact).abs().max())
+        far = float((restate(xp, torch.zeros_like(whh), B, H, W, hid, axis, torch.float64) - exact).abs().max())
+        err = float((LM.scan_model(xp, whh, B, H, W, hid, torch.float32, axis).double() - exact).abs().max())
+        assert 0.0 < gate <= 0.2 * far and err <= gate, (B, H, W, err, gate, far)
+
+
+@MODEL_CASES
+@AXES
+def test_the_model_passes_the_recurrence_checks(hid, dtype, axis):
+    """what tests/test_gpu_sequencer.py asks of the kernel, asked of the faultless model: the replay of every gate and permutation, the forget
+    gate's value check (whose condition gate <= far / 5 is a CPU figure: it holds here before anything runs on a GPU) and the identical lines"""
+    for kind in LM.KINDS:
+        for gate in ("i", "g", "o"):
+            assert LM.replay_check(model(), *MASK_MAP, hid, dtype, axis, gate, kind) > 0
+        LM.forget_check(model(), *MASK_MAP, hid, dtype, axis, kind)
+    LM.identical_check(model(), *MASK_MAP, hid, dtype, axis)
+
+
+# fault -> check -> the axes of MASK_MAP on which the check fails the faulty model ("vh": both, "h": axis 1 only, "": the check CANNOT see it).
+# replay, forget and identical are the checks of tests/test_gpu_sequencer.py.  What identical lines cannot see is common to all sequences; along
+# axis 0 the map has three sequences, so no second 16-sequence tile exists there for the map itself -- the replay still sees dead_subtile on both
+# axes because its single-step launch has B H W = 153 sequences.
+FAULT_TABLE = {
+    "k_swap": {"replay": "vh", "forget": "vh", "identical": ""},
+    "row_tile": {"replay": "vh", "forget": "vh", "identical": ""},
+    "dir_weights": {"replay": "vh", "forget": "vh", "identical": ""},
+    "stale_h": {"replay": "vh", "forget": "vh", "identical": ""},
+    "dead_subtile": {"replay": "vh", "forget": "h", "identical": "h"},
+}
+
+
+def fails(check):
+    try:
+        check()
+    except AssertionError:
+        return True
+    return False
+
+
+def test_the_fault_table_is_complete():
+    assert set(FAULT_TABLE) == set(LM.FAULTS)
+    for fault, row in FAULT_TABLE.items():
+        assert set(row) == {"replay", "forget", "identical"}
+        assert "".join(sorted(set(row["replay"] + row["identical"]))) == "hv", "%s: neither the replay nor the identical lines catch it on some axis" % fault
+    for fault in ("k_swap", "row_tile", "dir_weights"):
+        assert FAULT_TABLE[fault]["replay"] == "vh", fault
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+@pytest.mark.parametrize("hid", [32, 96])
+@pytest.mark.parametrize("fault", LM.FAULTS)
+def test_every_planted_fault_is_caught_where_the_table_says(fault, hid, dtype):
+    """every check against every faulty model on both axes: it fails exactly where FAULT_TABLE says.  The replay must fail for EVERY fed gate
+    and both permutations where it is listed, and pass for every one where it is not."""
+    m = model(fault)
+    for axis, tag in ((0, "v"), (1, "h")):
+        seen = {"replay": {fails(lambda: LM.replay_check(m, *MASK_MAP, hid, dtype, axis, gate, kind)) for gate in ("i", "g", "o") for kind in LM.KINDS},
+                "forget": {fails(lambda: LM.forget_check(m, *MASK_MAP, hid, dtype, axis, kind)) for kind in LM.KINDS},
+                "identical": {fails(lambda: LM.identical_check(m, *MASK_MAP, hid, dtype, axis))}}
+        for check, outcomes in seen.items():
+            assert outcomes == {tag in FAULT_TABLE[fault][check]}, (fault, check, "axis %d" % axis, outcomes)
+
+
+def test_row_tile_is_no_fault_with_one_unit_tile():
+    """hid 16 has one wave and one unit tile: the model with `row_tile` is the faultless model, bit for bit (why the table is held at hid 32, 96)"""
+    xp, whh = operands(*MASK_MAP, 16, torch.bfloat16, 5)
+    for axis in (0, 1):
+        assert torch.equal(LM.scan_model(xp, whh, *MASK_MAP, 16, torch.bfloat16, axis, "row_tile").view(torch.int16),
+                           LM.scan_model(xp, whh, *MASK_MAP, 16, torch.bfloat16, axis).view(torch.int16))
 
 
 # ------------------------------------------------------------------ the cache contract on the host
