@@ -534,6 +534,15 @@ int mlpk_s2_shift(int dtype, const void* in, void* out, int B, int H, int W, int
  * k odd, <= 13: 3 / 5 / 7 / 9 have the LDS-tiled and (16-bit, maps <= 32 x 32) matrix-core forms, the others the generic kernel.  An EVEN
  * kernel size of Conv2d(padding="same") pads (k - 1) / 2 before and k / 2 after: the caller passes it as the odd size k + 1 with a zero tap
  * row and column in front (models_pytorch/conv_mixer.py does).
+ * Held by tests/test_gpu_exact.py and tests/test_gpu_rounding.py over every form, tile and launch plan:
+ *   - bias, bn_scale, bn_shift may each be NULL and then mean 0, 1, 0: bit-equal to explicit vectors of those values, in all three forms;
+ *   - the matrix-core form rounds the taps to the storage type (they are MFMA operands); the LDS-tiled and the generic form use them as
+ *     fp32.  Products and sums are fp32 in all three, and the stored value is rounded once;
+ *   - an image's result does not depend on the batch it is in: image b of a batch is bit-equal to that image run alone (the form is
+ *     chosen from dtype, H, W, C, k and the alignment of x and out, never from B);
+ *   - refusals, before anything is launched and with `out` untouched: x, out or w NULL -> MLPK_ENULL; B, H, W or C <= 0, x == out (a
+ *     stencil cannot run in place), k even or outside 1 .. 13 -> MLPK_ESHAPE; a dtype other than MLPK_F32 / F16 / BF16 -> MLPK_EDTYPE,
+ *     whatever the shape.
  */
 int mlpk_dwconv_nhwc(int dtype, const void* x, void* out, int B, int H, int W, int C, int k,
                      const float* w, const float* bias, const float* bn_scale,

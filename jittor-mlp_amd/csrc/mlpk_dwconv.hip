@@ -156,6 +156,7 @@ static int dwconv_lds_launch(int k, const void* x, void* out, int B, int H, int 
     constexpr int CT = DwCfg<T>::CT;
     constexpr int EPV = 16 / (int)sizeof(T);
     const int P = (k - 1) / 2;
+    // (pitch, plane and the 160 KiB fit are restated by dwconv_form in tests/exact.py)
     // row pitch: W + 2P columns, plus room for the last strip's 16-element window, rounded to whole vectors
     const int strips = (W + 7) / 8;
     int pitch = (strips - 1) * 8 + ((8 + k - 1 + EPV - 1) / EPV) * EPV;
@@ -423,7 +424,7 @@ __global__ void __launch_bounds__(NW * 64) dwconv_mfma_kernel(const T* __restric
     constexpr int TBL_WAVE = CLDS * KS * DWM_NPAT * 16;
     static_assert(CG % 8 == 0 && (512 * CH8) % NT == 0 && CREG >= 1 && CREG <= CPW, "workgroup geometry");
     static_assert(KS * KS * CG * 4 <= PLANES_END, "tap staging fits the planes");
-    int gx = blockIdx.x, gy = blockIdx.y;
+    int gx = blockIdx.x, gy = blockIdx.y;                           // (the deal is restated by dwconv_redeal in tests/exact.py)
     if (gridDim.x % 8 == 0 && (gridDim.x * gridDim.y) % 64 == 0) {     // (else the plain order: the deal below needs whole rounds)
         const int id = blockIdx.x + gridDim.x * blockIdx.y;
         const int xcd = id & 7, l = id >> 3;                        // l: this XCD's l-th workgroup
@@ -693,6 +694,7 @@ static int dwconv_mfma_launch(int k, const void* x, void* out, int B, int H, int
     // images per workgroup: rounds of 256 workgroups (one per CU: the planes alone take 103 KB) x (images + about 2 images' worth of
     // set-up: taps, fragments, zeroing) -- the fewest image-times wins (1536 channels, 256 images: 48 groups x 16 ranges of 16 = 3
     // whole rounds)
+    // (groups, per, the grid, FULL and the kernel's re-deal condition are restated by dwconv_plan / dwconv_form in tests/exact.py)
     int per = 4;
     long long best = -1;
     const long long slots = 256;
@@ -720,7 +722,10 @@ extern "C" int mlpk_dwconv_nhwc(int dtype, const void* x, void* out, int B, int 
     if (!x || !out || !w) return MLPK_ENULL;
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return MLPK_ESHAPE;
     if (x == out) return MLPK_ESHAPE;                    // a stencil cannot run in place
+    // before any branch: the matrix-core branch below tells f16 from "anything else", and an unknown code once ran the bf16 kernel
+    if (dtype != MLPK_F32 && dtype != MLPK_F16 && dtype != MLPK_BF16) return MLPK_EDTYPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // (the selection below -- which of the three forms runs -- is restated by dwconv_form in tests/exact.py: the suite's coverage claim)
     const int es = dtype == MLPK_F32 ? 4 : 2;
     const bool fast_ok = (C % (16 / es) == 0) && (((uintptr_t)x & 15) == 0) && B <= 0x7fffffff;
     // matrix-pipe form: 16-bit dtypes, maps of up to 32 x 32, whole 8-channel groups

@@ -874,8 +874,126 @@ def token_mlp_ln_inputs(c, nimg, C, S):
     return x, mean, rstd, gamma, beta, x.reshape(nimg, S, C) + c.core.reshape(nimg, C, S).permute(0, 2, 1)
 
 
-# ------------------------------------------------------------------------------------------------- depthwise convolution (matrix-core form)
-DWCONV_CASES = [(3, 8, 8, 40, k) for k in (3, 7, 9)]         # (images, H, W, C, k): 16-bit, a map of at most 32 x 32, C % 8 == 0
+# ------------------------------------------------------------------------------------------------- depthwise convolution: three forms
+# mlpk_dwconv_nhwc is three kernels behind one entry point (csrc/mlpk_dwconv.hip, csrc/mlpk_remap.hip): the matrix-core form
+# (dwconv_mfma_kernel, 16-bit, maps of at most 32 x 32; FULL = a 32 x 32 map and whole groups of 32 channels), the LDS-tiled form
+# (dwconv_lds_kernel) and the generic one (mlpk_dwconv_direct).  dwconv_form / dwconv_plan / dwconv_redeal RESTATE the library's
+# selection -- they are the coverage claim of the table below (tests/test_exact_host.py asserts it), not the oracle: if they go stale,
+# the exact comparison still judges whatever kernel ran.
+DWCONV_OLD_CASES = [(3, 8, 8, 40, k) for k in (3, 7, 9)]     # the table before this one (kept as its first rows): only res[0][0] holds data
+# ((images, H, W, C, k), what the row reaches): every geometry once
+DWCONV_TABLE = [((3, 8, 8, 40, k), "one block of 16 x 16, a partial channel group, one image range") for k in (3, 7, 9)] + [
+    ((3, 8, 8, 40, 5), "... and k = 5"),
+    ((2, 17, 19, 40, 9), "all four blocks, odd W, the store's tail at x >= 16"),
+    ((2, 19, 17, 40, 7), "all four blocks, odd W, the store's tail at x >= 16"),
+    ((2, 31, 25, 32, 5), "all four blocks, odd W, the store's tail at x >= 16"),
+    ((2, 25, 31, 32, 3), "all four blocks, odd W, the store's tail at x >= 16"),
+] + [((3, 32, 32, 32, k), "FULL with the prefetch of the next image running") for k in (3, 5, 7, 9)] + [
+    ((2, 32, 32, 64, 9), "FULL, two channel groups"),
+    ((2, 32, 32, 40, 7), "a full map with a partial channel group: not FULL"),
+    ((6, 5, 6, 32, 5), "two image ranges, the last of 2 images"),
+    ((9, 4, 4, 8, 3), "three ranges, the last of 1 image"),
+    ((32, 4, 4, 256, 3), "a grid of 8 x 8 workgroups: the re-deal over the XCDs is on"),
+    ((29, 6, 6, 256, 9), "the re-deal with a partial last range"),
+    ((2, 1, 32, 8, 7), "one row"),
+    ((2, 32, 1, 8, 7), "one column"),
+    ((1, 1, 1, 8, 9), "one pixel"),
+    ((2, 33, 9, 32, 9), "H just past 32: the 16-bit LDS-tiled form"),
+    ((2, 9, 40, 32, 3), "LDS-tiled, five strips"),
+    ((2, 9, 37, 40, 5), "LDS-tiled, W % 8 != 0, a partial channel tile"),
+    ((1, 34, 34, 32, 7), "LDS-tiled, a 34 x 34 map at k = 7"),
+    ((1, 48, 40, 32, 9), "the staged tile is over 160 KiB: generic"),
+    ((1, 48, 40, 16, 9), "the staged tile is over 160 KiB: generic"),
+    ((2, 7, 9, 12, 3), "C % 8 != 0: generic in 16 bits, LDS-tiled in fp32"),
+    ((2, 7, 9, 20, 5), "C % 8 != 0: generic in 16 bits, LDS-tiled in fp32"),
+    ((2, 7, 9, 68, 3), "C % 8 != 0 and the generic kernel's second channel block of 64"),
+    ((2, 7, 9, 6, 3), "C % 4 != 0: generic in every type"),
+    ((2, 7, 9, 66, 3), "C % 4 != 0, second channel block"),
+    ((1, 6, 6, 8, 1), "k = 1: generic"),
+    ((1, 6, 6, 8, 11), "k = 11: generic"),
+    ((1, 20, 20, 40, 13), "k = 13: generic"),
+]
+DWCONV_CASES = [g for g, _ in DWCONV_TABLE]
+DWCONV_OFFSET_CASE = ((2, 9, 9, 16, 5), 4)                   # 16-bit, x starts 4 elements = 8 bytes into its buffer: generic
+DWCONV_SWEEP = [(3, 8, 8, 32, k) for k in (3, 5, 7, 9)]      # every tap in every channel slot: one-hot with off in range(k * k)
+DWCONV_BATCH = [(6, 5, 6, 32, 5), (9, 4, 4, 8, 3), (29, 6, 6, 256, 9), (3, 32, 32, 32, 9), (2, 33, 9, 32, 9), (2, 7, 9, 20, 5)]
+DWM_CPW, DWM_CREG = 4, {3: 4, 5: 4, 7: 3, 9: 2}              # dwconv_mfma_launch: cpw; creg_want (DWM_CREG7, DWM_CREG9), capped at cpw
+
+
+def dwconv_form(dtype, H, W, C, k, aligned=True):
+    """which kernel mlpk_dwconv_nhwc runs: "mfma_full" | "mfma" | "lds" | "direct".  aligned: x and out on 16-byte boundaries (False: x
+    is off one, which sends every type to the generic kernel)."""
+    es = 4 if dtype == torch.float32 else 2                  # mlpk_dwconv_nhwc: es
+    epv = 16 // es                                           # mlpk_dwconv_nhwc: 16 / es;  dwconv_lds_launch: EPV
+    fast_ok = C % epv == 0 and aligned                       # mlpk_dwconv_nhwc: fast_ok
+    tiled_k = k in (3, 5, 7, 9)                              # dwconv_mfma_launch: switch (k), default DW_NOFIT;  dwconv_lds_launch: k != 3 && ...
+    if fast_ok and es == 2 and H <= 32 and W <= 32 and C % 8 == 0 and tiled_k:      # mlpk_dwconv_nhwc: the matrix-pipe branch
+        return "mfma_full" if (H == 32 and W == 32 and C % 32 == 0) else "mfma"     # dwconv_mfma_launch: full (cg = 8 waves x 4 channels)
+    if fast_ok and tiled_k:
+        P = (k - 1) // 2                                     # dwconv_lds_launch: P
+        strips = (W + 7) // 8                                # dwconv_lds_launch: strips
+        pitch = (strips - 1) * 8 + ((8 + k - 1 + epv - 1) // epv) * epv             # dwconv_lds_launch: pitch
+        pitch = max(pitch, W + 2 * P)
+        pitch = (pitch + epv - 1) // epv * epv
+        plane = (H + 2 * P) * pitch                          # dwconv_lds_launch: plane, made an odd number of 16-byte slots
+        plane = (plane + epv - 1) // epv * epv
+        if (plane // epv) % 2 == 0:
+            plane += epv
+        ct = 16 if dtype == torch.float32 else 32            # DwCfg<T>::CT
+        if ct * plane * es <= 160 * 1024:                    # dwconv_lds_launch: lds > 160 * 1024 -> DW_NOFIT
+            return "lds"
+    return "direct"
+
+
+def dwconv_direct_reason(dtype, H, W, C, k, aligned=True):
+    """why a geometry reaches the generic kernel: "k" | "channels" | "alignment" | "fit" (None: it does not)"""
+    if dwconv_form(dtype, H, W, C, k, aligned) != "direct":
+        return None
+    if k not in (3, 5, 7, 9):
+        return "k"
+    if C % epc_of(dtype):
+        return "channels"
+    return "fit" if aligned else "alignment"
+
+
+def dwconv_plan(B, C):
+    """the matrix-core form's launch: (channel groups, image ranges, images per range, whether the kernel re-deals its workgroups)"""
+    groups = (C + 31) // 32                                  # dwconv_mfma_launch: groups (cg = 32)
+    per, best = 4, -1                                        # dwconv_mfma_launch: per, best
+    for cand in (32, 16, 8, 4):                              # dwconv_mfma_launch: for (cand = 32; cand >= 4; cand /= 2)
+        wgs = groups * ((B + cand - 1) // cand)
+        cost = ((wgs + 255) // 256) * (cand + 2)             # dwconv_mfma_launch: slots = 256; cost
+        if best < 0 or cost < best:
+            best, per = cost, cand
+    ranges = (B + per - 1) // per                            # dwconv_mfma_launch: grid.y
+    redeal = groups % 8 == 0 and (groups * ranges) % 64 == 0                        # dwconv_mfma_kernel: gridDim.x % 8 == 0 && ... % 64 == 0
+    return groups, ranges, per, redeal
+
+
+def dwconv_redeal(bx, by, groups, ranges):
+    """dwconv_mfma_kernel's five lines from blockIdx to (gx, gy) = (channel group, image range) when the re-deal is on"""
+    idx = bx + groups * by                                   # id
+    xcd, l = idx & 7, idx >> 3                               # xcd, l
+    oct_, octs = (l >> 3) * 8 + xcd, groups >> 3             # oct, octs
+    return (oct_ % octs) * 8 + (l & 7), oct_ // octs         # gx, gy
+
+
+def dwconv_patterns(dtype, geom):
+    """The patterns a geometry carries.  one-hot and ternary: all.  cancel needs (1) a 16-bit type -- its premise is an accumulator that
+    the storage type cannot hold, and fp32 holds every one of them -- and (2) a corner tap that is not the centre tap and reaches the
+    map: k > 1 and min(H, W) > k // 2 (without it every accumulator is 2^12 + 64 {0, 1}, which both 16-bit types hold)."""
+    B, H, W, C, k = geom
+    pats = ["onehot", "ternary"]
+    if dtype != torch.float32 and k > 1 and min(H, W) > k // 2:
+        pats.append("cancel")
+    return pats
+
+
+def dwconv_offsets(pattern, C, k, full=False):
+    """one-hot launches: offsets such that every tap occurs (full: every tap in EVERY channel)"""
+    if pattern != "onehot":
+        return [0]
+    return list(range(k * k)) if full else onehot_offsets(C, k * k)
 
 
 def dwconv_case(pattern, dtype, B, H, W, C, k, off=0, seed=11):
@@ -939,6 +1057,72 @@ def check_dwconv_case(c):
         assert c.w.abs().max().item() <= 2 and bool((c.w[c.K // 2] != 0).all())
     else:
         assert c.acc.min().item() >= 4096 and not representable(c.acc, c.dtype), (what, "the accumulator stays exact in 16 bits")
+
+
+# planted faults of the matrix-core form (tests/test_exact_host.py: which table sees which).  Each is ONE mistake in one region:
+#   block_10         block (ty, tx) = (1, 0) reads its plane rows 16 too low (the ty term of the row offset is lost)
+#   block_01         block (0, 1) reads its plane columns 16 too low (the tx term of the fragment offset is lost)
+#   tail_dropped     the per-pixel tail of the four-pixel store (W % 4 != 0) is not written for x0 >= 16: the cell keeps the input
+#   prefetch_behind  in a last range that is partial and not the only one, the prefetched registers are one image behind: image b > b0
+#                    is computed from image b - 1
+#   table_swap       in one channel slot j >= CREG (fragments built from the LDS table, k = 7 / 9) taps d and d + 1 of tap row i are
+#                    swapped; `swap` = (j, i, d)
+DW_FAULTS = ("block_10", "block_01", "tail_dropped", "prefetch_behind", "table_swap")
+
+
+def dwconv_fault_region(c, fault, swap=None):
+    """the outputs a planted fault can change: a bool mask over (B, H, W, C); all False where the fault's code does not run"""
+    B, H, W, C, k = c.geom
+    b, y, x, ch = torch.meshgrid(torch.arange(B), torch.arange(H), torch.arange(W), torch.arange(C), indexing="ij")
+    none = torch.zeros((B, H, W, C), dtype=torch.bool)
+    if not dwconv_form(c.dtype, H, W, C, k).startswith("mfma"):
+        return none
+    if fault == "block_10":
+        return (y >= 16) & (x < 16)
+    if fault == "block_01":
+        return (y < 16) & (x >= 16)
+    if fault == "tail_dropped":
+        x0 = x // 4 * 4
+        return (x0 >= 16) & (x0 + 3 >= W)
+    if fault == "prefetch_behind":
+        _, ranges, per, _ = dwconv_plan(B, C)
+        return (b > (ranges - 1) * per) if (ranges > 1 and B % per) else none
+    assert fault == "table_swap"
+    j, i, d = swap
+    assert j < DWM_CPW and i < k and d + 1 < k
+    return (ch % DWM_CPW == j) if j >= DWM_CREG[k] else none
+
+
+def dwconv_fault_model(c, fault, swap=None):
+    """the reference convolution with one planted fault: what such a kernel would store (float64); c.want where the fault cannot show"""
+    B, H, W, C, k = c.geom
+    got = c.want.clone()
+    if fault is None:
+        return got
+    region = dwconv_fault_region(c, fault, swap)
+    if not region.any():
+        return got
+    if fault == "tail_dropped":
+        got[region] = c.x.expand_as(got)[region]
+        return got
+    if fault == "prefetch_behind":
+        got[region] = c.want.roll(1, 0)[region]
+        return got
+    if fault == "block_10":
+        acc = c.acc.roll(16, 1)
+    elif fault == "block_01":
+        acc = c.acc.roll(16, 2)
+    else:
+        j, i, d = swap
+        w = c.w.clone()
+        sel = torch.arange(C) % DWM_CPW == j
+        w[i * k + d, sel], w[i * k + d + 1, sel] = c.w[i * k + d + 1, sel], c.w[i * k + d, sel]
+        acc = torch.nn.functional.conv2d(c.x.expand(B, H, W, C).permute(0, 3, 1, 2), w.t().reshape(C, 1, k, k), None, padding=k // 2, groups=C).permute(0, 2, 3, 1)
+    v = acc + c.bias
+    saturated = (v == v.round()) & (v >= GELU_THRESHOLD)                      # there every GELU form stores v itself
+    g = torch.where(saturated, v, 0.5 * v * (1.0 + torch.erf(v * 0.7071067811865476)))
+    got[region] = (c.x + g * c.bns + c.bnh)[region]
+    return got
 
 
 # ------------------------------------------------------------------------------------------------- mlpk_vip_branch

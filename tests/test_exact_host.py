@@ -1,6 +1,8 @@
 """The exact-integer oracle (tests/exact.py) checked on the CPU: its premises for every case table the GPU file uses, the GELU
 threshold from emulations of the three forms of csrc/mlpk_common.h, and a numpy model of a tiled GEMM with planted faults -- which
-pattern catches which fault, and that the Gaussian gate of tests/test_gpu_ops.py lets the two precision faults pass."""
+pattern catches which fault, and that the Gaussian gate of tests/test_gpu_ops.py lets the two precision faults pass.  For the depthwise
+convolution: what its geometry table reaches (a restatement of the dispatcher of csrc/mlpk_dwconv.hip), that no row can go, that the
+re-deal of its workgroups is a permutation, and planted faults of the matrix-core form that the earlier three-row table did not see."""
 import math
 
 import numpy as np
@@ -161,7 +163,7 @@ def test_premises_of_the_fused_kernel_cases():
                         xl, _, _, _, _, want = X.token_mlp_ln_inputs(c, nimg, C, S)
                         assert X.representable(xl, dtype)
                         X.check_mlp_case(c, hidden_dtype=hdt, residual=want.permute(0, 2, 1).reshape(nimg * C, S) - c.core)
-        for g in X.DWCONV_CASES:
+        for g in X.DWCONV_OLD_CASES:                             # (the whole table: test_premises_of_the_dwconv_table)
             for pat in X.PATTERNS:
                 for off in X.pattern_offsets(pat, g[3], g[4] ** 2):
                     X.check_dwconv_case(X.dwconv_case(pat, dtype, *g, off=off))
@@ -296,3 +298,224 @@ def test_gaussian_gate_passes_both_precision_faults_at_k_200():
     # the faults are real, and the rounding budget of tests/test_gpu_rounding.py (1.10 sqrt(1) x the floor) sees both
     assert err["bf16_acc"][1] > 1.5 * floor and err["round_before_bias"][1] > 1.10 * floor, (err, floor)
     assert gate > 8 * err[None][0]                                               # the gate is an order of magnitude above a correct kernel
+
+
+# ------------------------------------------------------------------------------------------------- depthwise convolution: the table
+@pytest.mark.parametrize("dtype", X.STORAGE)
+def test_premises_of_the_dwconv_table(dtype):
+    """every geometry x pattern x offset of exact.DWCONV_TABLE, fp32 included (GELU_THRESHOLD serves gelu_f too: the first test of this
+    file); the full tap sweep and the case whose x is off a 16-byte boundary.  cancel runs where dwconv_patterns says it can."""
+    n = 0
+    for g in X.DWCONV_CASES:
+        pats = X.dwconv_patterns(dtype, g)
+        assert pats[:2] == ["onehot", "ternary"]
+        for pat in pats:
+            for off in X.dwconv_offsets(pat, g[3], g[4]):
+                X.check_dwconv_case(X.dwconv_case(pat, dtype, *g, off=off))
+                n += 1
+    assert n >= len(X.DWCONV_CASES) * 2
+    if dtype != torch.float32:
+        carried = [g for g in X.DWCONV_CASES if "cancel" in X.dwconv_patterns(dtype, g)]
+        left = [g for g in X.DWCONV_CASES if g not in carried]
+        assert sorted(left) == sorted([(2, 1, 32, 8, 7), (2, 32, 1, 8, 7), (1, 1, 1, 8, 9), (1, 6, 6, 8, 1)]), left
+        for g in X.DWCONV_SWEEP:
+            for off in X.dwconv_offsets("onehot", g[3], g[4], full=True):
+                X.check_dwconv_case(X.dwconv_case("onehot", dtype, *g, off=off))
+        g, _ = X.DWCONV_OFFSET_CASE
+        for pat in X.dwconv_patterns(dtype, g):
+            X.check_dwconv_case(X.dwconv_case(pat, dtype, *g))
+    else:
+        assert all("cancel" not in X.dwconv_patterns(dtype, g) for g in X.DWCONV_CASES)
+
+
+def _dw_row(g):
+    B, H, W, C, k = g
+    groups, ranges, per, redeal = X.dwconv_plan(B, C)
+    f32, f16, bf16 = (X.dwconv_form(dt, H, W, C, k) for dt in X.STORAGE)
+    assert f16 == bf16
+    return dict(B=B, H=H, W=W, C=C, k=k, f32=f32, h=f16, groups=groups, ranges=ranges, per=per, redeal=redeal, last=B - (ranges - 1) * per,
+                why32=X.dwconv_direct_reason(torch.float32, H, W, C, k), why16=X.dwconv_direct_reason(torch.float16, H, W, C, k))
+
+
+# what the table claims to reach: (claim, predicate over one row as _dw_row describes it).  `h` is the 16-bit form, `last` the number
+# of images in the last range.  Every row of the table is the only one that serves some claim (the test below deletes each in turn).
+_MF = ("mfma", "mfma_full")
+DW_CLAIMS = [("lds in fp32", lambda r: r["f32"] == "lds"), ("direct in fp32", lambda r: r["f32"] == "direct")] + [
+    ("%s in 16 bits" % f, (lambda f: lambda r: r["h"] == f)(f)) for f in ("mfma_full", "mfma", "lds", "direct")]
+for _k in (3, 5, 7, 9):
+    DW_CLAIMS += [
+        ("mfma k=%d: one block, a partial second channel group, one range" % _k,
+         (lambda k: lambda r: r["h"] == "mfma" and r["k"] == k and r["H"] <= 16 and r["W"] <= 16 and r["C"] > 32 and r["C"] % 32 and r["ranges"] == 1)(_k)),
+        ("mfma k=%d: all four blocks and the store's tail at x >= 16" % _k,
+         (lambda k: lambda r: r["h"] == "mfma" and r["k"] == k and r["H"] > 16 and r["W"] > 16 and r["W"] % 4 != 0)(_k)),
+        ("mfma_full k=%d: one group, the prefetch runs" % _k,
+         (lambda k: lambda r: r["h"] == "mfma_full" and r["k"] == k and r["groups"] == 1 and min(r["B"], r["per"]) >= 2)(_k)),
+    ]
+DW_CLAIMS += [
+    ("mfma_full, two channel groups", lambda r: r["h"] == "mfma_full" and r["groups"] >= 2),
+    ("mfma, a full map that is not FULL", lambda r: r["h"] == "mfma" and r["H"] == 32 and r["W"] == 32),
+    ("mfma, several ranges, the last partial with a prefetch", lambda r: r["h"] in _MF and r["ranges"] > 1 and 2 <= r["last"] < r["per"] and not r["redeal"]),
+    ("mfma, three ranges, the last of one image", lambda r: r["h"] in _MF and r["ranges"] >= 3 and r["last"] == 1 and not r["redeal"]),
+    ("mfma, the re-deal with whole ranges", lambda r: r["h"] in _MF and r["redeal"] and r["last"] == r["per"]),
+    ("mfma, the re-deal with a partial last range", lambda r: r["h"] in _MF and r["redeal"] and r["last"] < r["per"]),
+    ("mfma, one row", lambda r: r["h"] in _MF and r["H"] == 1 and r["W"] > 1),
+    ("mfma, one column", lambda r: r["h"] in _MF and r["W"] == 1 and r["H"] > 1),
+    ("mfma, one pixel", lambda r: r["h"] in _MF and r["H"] == 1 and r["W"] == 1),
+    ("16-bit lds, H past 32 alone", lambda r: r["h"] == "lds" and r["H"] > 32 and r["W"] <= 32),
+    ("16-bit lds, five whole strips", lambda r: r["h"] == "lds" and r["W"] >= 40 and r["W"] % 8 == 0 and r["H"] <= 32),
+    ("16-bit lds, W % 8 != 0 and a partial channel tile", lambda r: r["h"] == "lds" and r["W"] % 8 != 0 and r["C"] % 32 != 0),
+    ("16-bit lds, H and W past 32", lambda r: r["h"] == "lds" and r["H"] > 32 and r["W"] > 32),
+    ("direct: the tile does not fit, whole channel tiles", lambda r: r["why16"] == "fit" and r["why32"] == "fit" and r["C"] % 32 == 0),
+    ("direct: the tile does not fit, a partial 16-bit channel tile", lambda r: r["why16"] == "fit" and r["why32"] == "fit" and r["C"] % 32 != 0),
+    ("direct in 16 bits for C % 8, lds in fp32, k = 3, one channel block", lambda r: r["why16"] == "channels" and r["f32"] == "lds" and r["k"] == 3 and r["C"] <= 64),
+    ("direct in 16 bits for C % 8, lds in fp32, k = 5", lambda r: r["why16"] == "channels" and r["f32"] == "lds" and r["k"] == 5),
+    ("direct in 16 bits for C % 8, lds in fp32, two channel blocks", lambda r: r["why16"] == "channels" and r["f32"] == "lds" and r["C"] > 64),
+    ("direct in fp32 for C % 4, one channel block", lambda r: r["why32"] == "channels" and r["C"] <= 64),
+    ("direct in fp32 for C % 4, two channel blocks", lambda r: r["why32"] == "channels" and r["C"] > 64),
+] + [("direct for k = %d" % k, (lambda k: lambda r: r["why16"] == "k" and r["why32"] == "k" and r["k"] == k)(k)) for k in (1, 11, 13)]
+
+
+def _dw_uncovered(table):
+    rows = [_dw_row(g) for g in table]
+    return [name for name, pred in DW_CLAIMS if not any(pred(r) for r in rows)]
+
+
+def test_the_dwconv_table_reaches_every_form_tile_and_plan():
+    """dwconv_form / dwconv_plan over the table: every form in every type that has it, both matrix-core instantiations at every k, all
+    four blocks with the store's tail, partial last ranges, the re-deal twice, the generic kernel for each of its four reasons"""
+    assert _dw_uncovered(X.DWCONV_CASES) == []
+    assert len(set(X.DWCONV_CASES)) == len(X.DWCONV_CASES) and X.DWCONV_CASES[:3] == X.DWCONV_OLD_CASES
+    # the fourth reason is x off a 16-byte boundary: no geometry has it, the offset case does (in 16 bits; it would be mfma otherwise)
+    (B, H, W, C, k), off = X.DWCONV_OFFSET_CASE
+    for dt in X.SIXTEEN:
+        assert (off * 2) % 16 != 0 and X.dwconv_form(dt, H, W, C, k) == "mfma" and X.dwconv_direct_reason(dt, H, W, C, k, aligned=False) == "alignment"
+    reasons = {X.dwconv_direct_reason(dt, *g[1:]) for g in X.DWCONV_CASES for dt in X.STORAGE} - {None}
+    assert reasons == {"k", "channels", "fit"}
+    # what the old table reached: one block of one instantiation, one range, no re-deal
+    old = [_dw_row(g) for g in X.DWCONV_OLD_CASES]
+    assert all(r["h"] == "mfma" and r["H"] <= 16 and r["W"] <= 16 and r["ranges"] == 1 and not r["redeal"] for r in old)
+    # every geometry of the batch test spans more than one image, and the three forms are among them
+    assert {X.dwconv_form(torch.bfloat16, *g[1:]).split("_")[0] for g in X.DWCONV_BATCH} == {"mfma", "lds", "direct"}
+    assert all(g in X.DWCONV_CASES and g[0] >= 2 for g in X.DWCONV_BATCH)
+
+
+@pytest.mark.parametrize("row", range(len(X.DWCONV_CASES)))
+def test_every_row_of_the_dwconv_table_is_needed(row):
+    """with any single row deleted some claim is left without a geometry"""
+    rest = X.DWCONV_CASES[:row] + X.DWCONV_CASES[row + 1:]
+    assert _dw_uncovered(rest) != [], X.DWCONV_TABLE[row]
+
+
+def test_the_dwconv_redeal_is_a_permutation():
+    """the kernel's map from blockIdx to (channel group, image range) is a bijection onto the grid wherever its condition turns it on;
+    the 8 workgroups that start together on one XCD (ids congruent mod 8 in one round of 64) are 8 neighbouring groups of one range"""
+    n = 0
+    for groups in range(8, 65, 8):
+        for ranges in range(1, 65):
+            if (groups * ranges) % 64:
+                continue
+            seen = {X.dwconv_redeal(bx, by, groups, ranges) for by in range(ranges) for bx in range(groups)}
+            assert seen == {(gx, gy) for gy in range(ranges) for gx in range(groups)}, (groups, ranges)
+            for rnd0 in range(0, groups * ranges, 64):
+                for xcd in range(8):
+                    got = [X.dwconv_redeal(i % groups, i // groups, groups, ranges) for i in range(rnd0 + xcd, rnd0 + 64, 8)]
+                    assert len({gy for _, gy in got}) == 1 and sorted(gx for gx, _ in got) == list(range(got[0][0] // 8 * 8, got[0][0] // 8 * 8 + 8))
+            n += 1
+    assert n > 50
+    for g in X.DWCONV_CASES:                                 # the plan's condition is the one under which the map above is used
+        groups, ranges, per, redeal = X.dwconv_plan(g[0], g[3])
+        assert redeal == (groups % 8 == 0 and (groups * ranges) % 64 == 0) and (ranges - 1) * per < g[0] <= ranges * per
+
+
+# ------------------------------------------------------------------------------------------------- depthwise convolution: planted faults
+def _dw_cases(table, dtype, old):
+    """the launches of a table: the old one ran every pattern with the offsets of onehot_offsets; the new one adds the full tap sweep"""
+    for g in table:
+        for pat in (X.PATTERNS if old else X.dwconv_patterns(dtype, g)):
+            for off in X.dwconv_offsets(pat, g[3], g[4]):
+                yield (pat, g, off)
+    if not old:
+        for g in X.DWCONV_SWEEP:
+            for off in X.dwconv_offsets("onehot", g[3], g[4], full=True):
+                yield ("onehot", g, off)
+
+
+_DW_CACHE = {}
+
+
+def _dw_case(pat, dtype, g, off):
+    key = (pat, dtype, g, off)
+    if key not in _DW_CACHE:
+        _DW_CACHE[key] = X.dwconv_case(pat, dtype, *g, off=off)
+    return _DW_CACHE[key]
+
+
+def _dw_sees(table, old, fault, swap=None, dtype=torch.bfloat16, k=None):
+    """the first launch of a table whose exact comparison fails under the planted fault (None: the table is blind to it)"""
+    for (pat, g, off) in _dw_cases(table, dtype, old):
+        if k is not None and g[4] != k:
+            continue
+        if fault == "table_swap":
+            if g[4] not in (7, 9) or swap[0] < X.DWM_CREG[g[4]] or swap[1] >= g[4] or swap[2] + 1 >= g[4]:
+                continue                                     # no table fragment, or no such tap, at this k
+        elif pat != "onehot" and not old:
+            continue                                         # (one pattern is enough to show that the new table sees a region fault)
+        c = _dw_case(pat, dtype, g, off)
+        if fault == "table_swap":
+            t = swap[1] * g[4] + swap[2]
+            sel = torch.arange(g[3]) % X.DWM_CPW == swap[0]
+            if torch.equal(c.w[t, sel], c.w[t + 1, sel]):
+                continue                                     # (exact, and cheap: equal taps swapped are the same taps)
+        got = X.dwconv_fault_model(c, fault, swap)
+        try:
+            X.assert_exact(got, c.want, fault)
+        except AssertionError as e:
+            e.case = (pat, g, off)
+            return e
+    return None
+
+
+@pytest.mark.parametrize("fault", X.DW_FAULTS[:4])
+def test_planted_dwconv_region_fault(fault):
+    """the record of why the rows are there: the old three-row table with its one-hot sweep is blind to each of these faults of the
+    matrix-core form, and the new table names an element inside the fault's region"""
+    assert _dw_sees(X.DWCONV_OLD_CASES, True, fault) is None
+    for (pat, g, off) in _dw_cases(X.DWCONV_OLD_CASES, torch.bfloat16, True):
+        c = _dw_case(pat, torch.bfloat16, g, off)
+        X.assert_exact(X.dwconv_fault_model(c, None), c.want, "the fault-free model is the reference")
+    e = _dw_sees(X.DWCONV_CASES, False, fault)
+    assert e is not None, fault
+    b, y, x, ch = e.index
+    (B, H, W, C, k) = e.case[1]
+    if fault == "block_10":
+        assert y >= 16 and x < 16
+    elif fault == "block_01":
+        assert y < 16 and x >= 16
+    elif fault == "tail_dropped":
+        assert x >= 16 and x // 4 * 4 + 3 >= W and W % 4 != 0
+    else:
+        _, ranges, per, _ = X.dwconv_plan(B, C)
+        assert ranges > 1 and b > (ranges - 1) * per
+
+
+def test_planted_dwconv_table_swap():
+    """every (slot j >= CREG, tap row i, d) swap of the LDS-table fragments at k = 7 and k = 9 -- 186 faults.  The old table, whose
+    one-hot sweep gives a channel 3 of its 81 taps, is blind to some of them (its ternary taps are sparse); the new table, whose
+    sweep gives every channel every tap, sees every one and names a channel of the slot."""
+    blind_old, total = [], 0
+    for k in (7, 9):
+        for j in range(X.DWM_CREG[k], X.DWM_CPW):
+            for i in range(k):
+                for d in range(k - 1):
+                    swap = (j, i, d)
+                    total += 1
+                    if _dw_sees(X.DWCONV_OLD_CASES, True, "table_swap", swap, k=k) is None:
+                        blind_old.append((k,) + swap)
+                    new = _dw_sees(X.DWCONV_CASES, False, "table_swap", swap, k=k)
+                    assert new is not None and new.index[3] % X.DWM_CPW == j, (k, swap)
+    assert total == 7 * 6 + 2 * 9 * 8
+    assert blind_old, "the old table saw every planted swap"
+    print("table_swap: the old table is blind to %d of %d swaps, e.g. %s" % (len(blind_old), total, blind_old[:4]))
+    # a register-held slot is not a table fragment: the fault has no region there
+    c = _dw_case("onehot", torch.bfloat16, X.DWCONV_SWEEP[3], 0)
+    assert not X.dwconv_fault_region(c, "table_swap", (0, 0, 0)).any() and X.dwconv_fault_region(c, "table_swap", (3, 0, 0)).any()

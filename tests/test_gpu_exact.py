@@ -384,23 +384,146 @@ def test_token_mlp_generated_kernel_and_prenorm(dtype, nch):
             X.assert_exact(part, X.token_stats_want(want.reshape(nimg * S, C), planes), "token_mlp_ln stats " + what)
 
 
-# ------------------------------------------------------------------------------------------------- mlpk_dwconv_nhwc, the matrix-core form
-@pytest.mark.parametrize("dtype", X.SIXTEEN)
-def test_dwconv_matrix_core(dtype):
-    """k = 3 / 7 / 9 on an 8 x 8 map, 40 channels (a partial group of 32), saturated GELU; the one-hot taps name (tap, channel)"""
+# ------------------------------------------------------------------------------------------------- mlpk_dwconv_nhwc: every form, tile and launch plan
+DW_GROUPS = ("mfma", "mfma_full", "lds", "direct")           # a geometry's group is the form its 16-bit run takes (exact.dwconv_form)
+DW_ENULL, DW_ESHAPE, DW_EDTYPE = -4, -2, -1                  # include/mlpk.h
+
+
+def run_dwconv(c, x_off=0):
+    """one mlpk_dwconv_nhwc call for an exact.dwconv_case into a NaN-filled out; x_off: x starts that many elements into its buffer"""
     E = load_pkg().engine
     f = torch.float32
+    B, H, W, C, k = c.geom
+    x = put(c.x, c.dtype)
+    if x_off:
+        buf = torch.zeros(x.numel() + x_off, dtype=c.dtype, device=dev())
+        buf[x_off:] = x.reshape(-1)
+        x = buf[x_off:].view(B, H, W, C)
+        assert x.data_ptr() % 16 == (x_off * x.element_size()) % 16 != 0
+    out = torch.full((B, H, W, C), float("nan"), dtype=c.dtype, device=dev())
+    E.dwconv_nhwc(x, out, B, H, W, C, k, put(c.w, f), put(c.bias, f), put(c.bns, f), put(c.bnh, f))
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("dtype", X.STORAGE)
+@pytest.mark.parametrize("group", DW_GROUPS)
+def test_dwconv_matrix_core(dtype, group):
+    """exact.DWCONV_TABLE: the matrix-core form (both instantiations, k = 3 / 5 / 7 / 9, all four 16 x 16 blocks, the store's tail, several
+    image ranges, the re-deal over the XCDs, degenerate maps), the LDS-tiled and the generic form, in all three storage types (fp32 runs
+    the LDS-tiled or the generic kernel on the same geometries).  Saturated GELU; the one-hot taps name (tap, channel); zero differing
+    elements is the gate."""
+    n = 0
     for geom in X.DWCONV_CASES:
         B, H, W, C, k = geom
-        for pat in X.PATTERNS:
-            for off in X.pattern_offsets(pat, C, k * k):
+        if X.dwconv_form(torch.bfloat16, H, W, C, k) != group:
+            continue
+        for pat in X.dwconv_patterns(dtype, geom):
+            for off in X.dwconv_offsets(pat, C, k):
                 c = X.dwconv_case(pat, dtype, *geom, off=off)
                 X.check_dwconv_case(c)
-                x = put(c.x, dtype)
-                out = torch.full_like(x, float("nan"))
-                E.dwconv_nhwc(x, out, B, H, W, C, k, put(c.w, f), put(c.bias, f), put(c.bns, f), put(c.bnh, f))
-                torch.cuda.synchronize()
-                X.assert_exact(out, c.want, "dwconv %s %s %s" % (pat, dtype, geom), K=k * k if pat == "onehot" else None, k_off=off)
+                X.assert_exact(run_dwconv(c), c.want, "dwconv %s %s %s" % (pat, dtype, geom), K=k * k if pat == "onehot" else None, k_off=off)
+                n += 1
+    assert n > 0
+    if group == "direct" and dtype != torch.float32:          # the fourth way to the generic kernel: x off a 16-byte boundary
+        geom, x_off = X.DWCONV_OFFSET_CASE
+        for pat in X.dwconv_patterns(dtype, geom):
+            c = X.dwconv_case(pat, dtype, *geom)
+            X.check_dwconv_case(c)
+            X.assert_exact(run_dwconv(c, x_off), c.want, "dwconv %s %s %s x + %d" % (pat, dtype, geom, x_off), K=geom[4] ** 2 if pat == "onehot" else None)
+
+
+@pytest.mark.parametrize("dtype", X.SIXTEEN)
+@pytest.mark.parametrize("k", [3, 5, 7, 9])
+def test_dwconv_every_tap_in_every_channel_slot(dtype, k):
+    """one-hot with every offset on (3, 8, 8, 32, k): each channel slot of each wave meets each of the k k taps, the fragments held in
+    registers (tf[j][i]) and those read from the LDS table alike -- the table's own sweep gives a channel 1 .. 3 of them"""
+    geom = [g for g in X.DWCONV_SWEEP if g[4] == k][0]
+    assert X.dwconv_form(dtype, *geom[1:]) == "mfma"
+    for off in X.dwconv_offsets("onehot", geom[3], k, full=True):
+        c = X.dwconv_case("onehot", dtype, *geom, off=off)
+        X.check_dwconv_case(c)
+        X.assert_exact(run_dwconv(c), c.want, "dwconv tap sweep %s %s off %d" % (dtype, geom, off), K=k * k, k_off=off)
+
+
+def _dw_gaussian(dtype, geom, seed):
+    B, H, W, C, k = geom
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn((B, H, W, C), generator=g).to(dtype).to(dev())
+    w = (torch.randn((k * k, C), generator=g) / k).to(dev())
+    bias, bns, bnh = torch.randn((C,), generator=g).to(dev()), (torch.randn((C,), generator=g) * 0.2 + 1).to(dev()), torch.randn((C,), generator=g).to(dev())
+    return x, w, bias, bns, bnh
+
+
+@pytest.mark.parametrize("dtype", X.STORAGE)
+def test_dwconv_image_does_not_depend_on_its_batch(dtype):
+    """Gaussian data, all three forms, batches that span several image ranges and the re-deal: image b of the batch is bit-equal to the
+    same image run alone (B = 1: one range, no prefetch, the plain workgroup order)"""
+    E = load_pkg().engine
+    for geom in X.DWCONV_BATCH:
+        B, H, W, C, k = geom
+        x, w, bias, bns, bnh = _dw_gaussian(dtype, geom, 41)
+        out = torch.full_like(x, float("nan"))
+        E.dwconv_nhwc(x, out, B, H, W, C, k, w, bias, bns, bnh)
+        alone = torch.full_like(x, float("nan"))
+        for b in range(B):
+            E.dwconv_nhwc(x[b], alone[b], 1, H, W, C, k, w, bias, bns, bnh)
+        torch.cuda.synchronize()
+        assert torch.isfinite(out).all()
+        X.assert_exact(out, alone.cpu().double(), "dwconv batch %s %s: (image, y, x, channel)" % (dtype, geom))
+
+
+@pytest.mark.parametrize("dtype", X.STORAGE)
+def test_dwconv_null_epilogue_vectors(dtype):
+    """bias / bn_scale / bn_shift NULL mean 0 / 1 / 0 in all three kernels: bit-equal to explicit vectors, one geometry per form"""
+    E = load_pkg().engine
+    forms = set()
+    for geom in [(2, 19, 17, 40, 7), (3, 32, 32, 32, 9), (2, 9, 37, 40, 5), (2, 7, 9, 66, 3)]:
+        B, H, W, C, k = geom
+        assert geom in X.DWCONV_CASES
+        forms.add(X.dwconv_form(dtype, H, W, C, k))
+        x, w, bias, bns, bnh = _dw_gaussian(dtype, geom, 43)
+        zero, one = torch.zeros_like(bias), torch.ones_like(bias)
+        for null in range(1, 8):                             # every non-empty subset of the three
+            given = [None if null & 1 else bias, None if null & 2 else bns, None if null & 4 else bnh]
+            explicit = [zero if null & 1 else bias, one if null & 2 else bns, zero if null & 4 else bnh]
+            got, want = torch.full_like(x, float("nan")), torch.full_like(x, float("nan"))
+            E.dwconv_nhwc(x, got, B, H, W, C, k, w, *given)
+            E.dwconv_nhwc(x, want, B, H, W, C, k, w, *explicit)
+            torch.cuda.synchronize()
+            assert torch.isfinite(want).all()
+            X.assert_exact(got, want.cpu().double(), "dwconv NULL mask %d %s %s" % (null, dtype, geom))
+    assert forms == ({"lds", "direct"} if dtype == torch.float32 else {"mfma", "mfma_full", "lds", "direct"})
+
+
+def test_dwconv_refusals():
+    """every documented refusal returns its code before anything is launched: the NaN-filled output stays NaN.  Small = a map of at most
+    32 x 32 with C % 8 == 0 (the matrix-core branch in 16 bits), large = 40 x 40."""
+    E, N = load_pkg().engine, load_pkg()._native
+    L, s = N.lib(), E.stream()
+    w = torch.ones((15 * 15, 8), device=dev())
+    vec = torch.ones((8,), device=dev())
+    cases = []
+    for name, (H, W) in (("small", (8, 8)), ("large", (40, 40))):
+        for dt, code in ((torch.float32, 0), (torch.float16, 1), (torch.bfloat16, 2)):
+            x = torch.ones((1, H, W, 8), dtype=dt, device=dev())
+            out = torch.full_like(x, float("nan"))
+
+            def args(k=3, xx=x, oo=out, ww=w, cc=code, H=H, W=W):
+                return (cc, E.ptr(xx), E.ptr(oo), 1, H, W, 8, k, E.ptr(ww), vec.data_ptr(), vec.data_ptr(), vec.data_ptr(), s)
+            cases +=[("%s %s x NULL" % (name, dt), DW_ENULL, args(xx=None), out), ("%s %s out NULL" % (name, dt), DW_ENULL, args(oo=None), out),
+                      ("%s %s w NULL" % (name, dt), DW_ENULL, args(ww=None), out), ("%s %s x == out" % (name, dt), DW_ESHAPE, args(xx=out), out)]
+            cases += [("%s %s k = %d" % (name, dt, k), DW_ESHAPE, args(k=k), out) for k in (0, 2, 4, 15)]
+            if dt == torch.bfloat16:                         # (a 16-bit buffer: what an unknown code was once taken for)
+                cases += [("%s dtype %d" % (name, bad), DW_EDTYPE, args(cc=bad), out) for bad in (3, -1)]
+    for what, want, a, out in cases:
+        rc = L.mlpk_dwconv_nhwc(*a)
+        torch.cuda.synchronize()
+        assert rc == want, (what, rc, want)
+        assert torch.isnan(out).all(), (what, "the output was written")
+    # (the wrapper raises on any of them)
+    with pytest.raises(N.MlpkError):
+        E.dwconv_nhwc(out, out, 1, 40, 40, 8, 3, w, vec, vec, vec)
 
 
 # ------------------------------------------------------------------------------------------------- mlpk_vip_branch

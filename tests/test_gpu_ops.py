@@ -413,7 +413,11 @@ def test_s2_shift_and_split_attention(golden_dir):
 def test_dwconv(dtype):
     pkg = load_pkg()
     E = pkg.engine
-    for (B_, H, W, C, k) in [(2, 8, 8, 32, 5), (1, 32, 32, 64, 9), (2, 7, 9, 16, 3)]:
+    # rows of exact.DWCONV_TABLE behind the first three shapes: maps that cross the matrix-core form's 16 x 16 blocks, the LDS-tiled form in 16
+    # bits, the generic kernel (tile over 160 KiB, C % 8, C % 4, k = 1 / 11 / 13).  The 16-bit forms' rounding: tests/test_gpu_rounding.py.
+    table = [(2, 17, 19, 40, 9), (2, 19, 17, 40, 7), (2, 31, 25, 32, 5), (2, 25, 31, 32, 3), (2, 33, 9, 32, 9), (2, 9, 40, 32, 3), (2, 9, 37, 40, 5),
+             (1, 34, 34, 32, 7), (1, 48, 40, 16, 9), (2, 7, 9, 20, 5), (2, 7, 9, 66, 3), (1, 6, 6, 8, 1), (1, 6, 6, 8, 11), (1, 20, 20, 40, 13)]
+    for (B_, H, W, C, k) in [(2, 8, 8, 32, 5), (1, 32, 32, 64, 9), (2, 7, 9, 16, 3)] + table:
         x = rnd((B_, H, W, C), dtype, 31).to(dev())
         w = rnd((C, 1, k, k), torch.float32, 32, 1.0 / k)
         bias = rnd((C,), torch.float32, 33)

@@ -237,3 +237,37 @@ def test_patch_embed4_and_stem7(dtype):
         torch.cuda.synchronize()
         ref = F.conv2d(x.double(), wconv.to(dtype).double(), bias.double(), stride=4, padding=pad).permute(0, 2, 3, 1).reshape(-1, C)
         budget("stem7", dtype, (out.shape[0], C, 147), out, ref, 1)
+
+
+# mlpk_dwconv_nhwc: one geometry of exact.DWCONV_TABLE per form and per k the form has
+DWCONV_ROUNDING = {
+    "mfma": [(2, 25, 31, 32, 3), (2, 31, 25, 32, 5), (2, 19, 17, 40, 7), (2, 17, 19, 40, 9)],
+    "mfma_full": [(3, 32, 32, 32, k) for k in (3, 5, 7, 9)],
+    "lds": [(2, 9, 40, 32, 3), (2, 9, 37, 40, 5), (1, 34, 34, 32, 7), (2, 33, 9, 32, 9)],
+    "direct": [(1, 6, 6, 8, 1), (2, 7, 9, 68, 3), (2, 7, 9, 20, 5), (1, 48, 40, 32, 9), (1, 6, 6, 8, 11), (1, 20, 20, 40, 13)],
+}
+
+
+@pytest.mark.parametrize("dtype", SIXTEEN)
+@pytest.mark.parametrize("form", sorted(DWCONV_ROUNDING))
+def test_dwconv(dtype, form):
+    """out = x + gelu(dw_k(x) + bias) bn_scale + bn_shift on Gaussian data with a non-trivial bn_scale: fp32 products and sums, the GELU
+    (gelu_pk_n in the matrix-core and the LDS-tiled kernel, gelu_f in the generic one), ONE rounding at the store in all three kernels.
+    The matrix-core form rounds the taps to the storage type (they are MFMA operands: mlpk.h), so its reference multiplies the rounded
+    taps; the other two forms take them as fp32."""
+    E = load_pkg().engine
+    for (B, H, W, C, k) in DWCONV_ROUNDING[form]:
+        assert (B, H, W, C, k) in X.DWCONV_CASES and X.dwconv_form(dtype, H, W, C, k) == form
+        x = rnd((B, H, W, C), dtype, 700 + k)
+        w = rnd((C, 1, k, k), torch.float32, 701 + k, 1.0 / k)
+        bias = rnd((C,), torch.float32, 702 + k)
+        bns = rnd((C,), torch.float32, 703 + k) * 0.2 + 1
+        bnh = rnd((C,), torch.float32, 704 + k)
+        out = torch.full((B, H, W, C), float("nan"), dtype=dtype, device=dev())
+        E.dwconv_nhwc(x.to(dev()), out, B, H, W, C, k, w.reshape(C, k * k).t().contiguous().to(dev()), bias.to(dev()), bns.to(dev()), bnh.to(dev()))
+        torch.cuda.synchronize()
+        wr = (w.to(dtype) if form.startswith("mfma") else w).double()
+        xn = x.double().permute(0, 3, 1, 2)
+        d = torch.nn.functional.conv2d(xn, wr, bias.double(), padding=k // 2, groups=C)
+        ref = (xn + oracle.gelu(d) * bns.double().view(1, C, 1, 1) + bnh.double().view(1, C, 1, 1)).permute(0, 2, 3, 1)
+        budget("dwconv_nhwc %s k=%d" % (form, k), dtype, (B, H, W, C), out, ref, 1)
