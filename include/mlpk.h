@@ -68,6 +68,8 @@
  *                       in registers, the h W_hh product of every step on the matrix pipe
  *   mlpk_dwconv_nhwc    depthwise Conv2d(k, groups=dim, padding="same") + GELU + BatchNorm(eval) + residual:
  *                       conv_mixer.py:5-11,24-28
+ *   mlpk_ln_dwconv3_nhwc, mlpk_relu_add, mlpk_relu_maxpool3s2_nhwc   ConvMLP (conv_mlp.py:51-87,108-126,155-168): connect(connect_norm(x)) in one
+ *                       pass, the ReLU behind a BatchNorm with the stage's residual, and the tokenizer's ReLU + MaxPool2d(3, 2, 1)
  */
 #ifndef MLPK_H
 #define MLPK_H
@@ -876,6 +878,36 @@ int mlpk_dyna_mix_logits(int dtype, const void* x, int64_t x_pitch, const float*
 int mlpk_lstm_scan_supported(int dtype, int L, int hid);
 int mlpk_lstm_scan(int dtype, const void* xp, int64_t xp_pitch, int xp_off, const void* whh, void* out, int64_t out_pitch, int out_off, int B, int H,
                    int W, int hid, int axis, void* stream);
+
+/* ConvMLP's three passes over whole activations (conv_mlp.py): the depthwise `connect` convolution behind its LayerNorm (ConvMLPStage :155-168),
+ * the ReLU that follows a BatchNorm (ConvTokenizer :63-79, ConvStage :108-114, with the stage's residual :125), and the tokenizer's ReLU +
+ * MaxPool2d(3, 2, 1) (:79-83).  Every operand is a DENSE channel-last tensor -- rows of C channels at row pitch C, as in mlpk_dwconv_nhwc -- in
+ * fp32, fp16 or bf16, moved in 16-byte vectors: C (n for mlpk_relu_add) must be a whole number of vectors, C % 8 == 0 for the 16-bit types, C % 4
+ * == 0 for fp32.  No scratch memory, no state.
+ *
+ * mlpk_ln_dwconv3_nhwc: out = connect(connect_norm(x)) for x, out (B, H, W, C).  The operand is v[b,y,x,c] = round_to_storage((x[b,y,x,c] -
+ *   mean[pix]) rstd[pix] gamma[c] + beta[c]) inside the map -- the expression and rounding of mlpk_norm_apply, never stored -- and EXACTLY 0 outside
+ *   it: the zero padding follows the norm, it is not beta[c].  out[b,y,x,c] = sum over i, j < 3 of w[(3 i + j) C + c] v[b, y + i - 1, x + j - 1, c],
+ *   accumulated in fp32 from 0 in that tap order, one fused multiply-add per tap, rounded once.  mean / rstd per pixel (B H W, fp32), both NULL:
+ *   0 / 1; gamma / beta per channel, NULL: 1 / 0; w fp32 [9][C] tap-major, the layout of mlpk_dwconv_nhwc; no bias, no residual.  A workgroup stages
+ *   the halo of an 8 x 16 pixel tile of up to 8 channel vectors in LDS (22.5 KiB), so every input pixel is normalised once per workgroup, not once
+ *   per tap.  An image's result does not depend on the batch it is in: the launch plan follows from dtype, H, W and C, B only multiplies the grid.
+ * mlpk_relu_add: out[i] = round(float(res[i]) + max(float(y[i]), 0)), i < n, one rounding; res NULL: out = relu(y).  A NaN in y stays a NaN.  out
+ *   may be y or res (every vector is read before it is written).
+ * mlpk_relu_maxpool3s2_nhwc: out[b,yo,xo,c] = max(0, max of y[b,yy,xx,c] over the pixels of the 3 x 3 window at (2 yo - 1, 2 xo - 1) that lie
+ *   inside the map), out (B, Ho, Wo, C) with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1: MaxPool2d(3, 2, 1) of relu(y); the padding never wins.  A NaN
+ *   inside a window is the window's result, as in torch and as mlpk_relu_add keeps one.  Cannot run in place.
+ * All three return before anything is launched and leave the outputs untouched: a missing pointer (x / y, out, w; only one of mean / rstd)
+ * MLPK_ENULL; a dtype other than fp32 / fp16 / bf16 MLPK_EDTYPE, whatever the shape; a non-positive extent, C (n) off the vector, a grid of more
+ * than 2^31 - 1 workgroups, or x == out / y == out where a stencil cannot run in place (the first and the third) MLPK_ESHAPE; x, y, res or out off a
+ * 16-byte boundary MLPK_EALIGN.  Each *_supported twin answers 1 exactly where its entry accepts the dtype and the extents, else 0. */
+int mlpk_ln_dwconv3_nhwc_supported(int dtype, int B, int H, int W, int C);
+int mlpk_ln_dwconv3_nhwc(int dtype, const void* x, const float* mean, const float* rstd, const float* gamma, const float* beta, const float* w,
+                         void* out, int B, int H, int W, int C, void* stream);
+int mlpk_relu_add_supported(int dtype, int64_t n);
+int mlpk_relu_add(int dtype, const void* y, const void* res, void* out, int64_t n, void* stream);
+int mlpk_relu_maxpool3s2_nhwc_supported(int dtype, int B, int H, int W, int C);
+int mlpk_relu_maxpool3s2_nhwc(int dtype, const void* y, void* out, int B, int H, int W, int C, void* stream);
 
 /* Tile-height plan of the persistent GEMM tile, process-wide (round 6): 0 (default) = mixed tile heights, the shortest SINGLE launch (Mixer-B fc2: 588 tiles on
  * 256 CUs run as 2.58 instead of 3 round-times); 1 = whole 256-row tiles only wherever they still fill a round of CUs and K >= 1024, the least TOTAL CU time (3 % less for that

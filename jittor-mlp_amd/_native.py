@@ -171,6 +171,15 @@ PROTOTYPES = {
     "mlpk_lstm_scan_supported": (c_int, [c_int] * 3),
     # (dtype, xp, xp_pitch, xp_off, whh, out, out_pitch, out_off, B, H, W, hid, axis, stream)
     "mlpk_lstm_scan": (c_int, [c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_i64, c_int] + [c_int] * 5 + [c_void_p]),
+    "mlpk_ln_dwconv3_nhwc_supported": (c_int, [c_int] * 5),
+    # (dtype, x, mean, rstd, gamma, beta, w, out, B, H, W, C, stream)
+    "mlpk_ln_dwconv3_nhwc": (c_int, [c_int] + [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
+    "mlpk_relu_add_supported": (c_int, [c_int, c_i64]),
+    # (dtype, y, res, out, n, stream)
+    "mlpk_relu_add": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    "mlpk_relu_maxpool3s2_nhwc_supported": (c_int, [c_int] * 5),
+    # (dtype, y, out, B, H, W, C, stream)
+    "mlpk_relu_maxpool3s2_nhwc": (c_int, [c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
 }
 
 _lib = None

@@ -838,6 +838,35 @@ def lstm_scan(xp, xp_off, whh, out, out_off, B, H, W, hid, axis):
                                    axis, stream()), "mlpk_lstm_scan")
 
 
+def ln_dwconv3_supported(dtype, B, H, W, C):
+    return bool(N.lib().mlpk_ln_dwconv3_nhwc_supported(dtype_code(dtype), B, H, W, C))
+
+
+def ln_dwconv3_nhwc(x, mean, rstd, gamma, beta, w, out, B, H, W, C):
+    """ConvMLP's connect(connect_norm(x)) on dense channel-last rows (mlpk_ln_dwconv3_nhwc): out = the bias-free depthwise 3 x 3 (w fp32 [9][C]) of
+    LayerNorm(x), zero padding after the norm; mean / rstd per pixel, gamma / beta per channel (any of the pairs None: 0 / 1, 1 / 0)"""
+    N.check(N.lib().mlpk_ln_dwconv3_nhwc(dtype_code(x.dtype), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(w), ptr(out), B, H, W, C,
+                                         stream()), "mlpk_ln_dwconv3_nhwc")
+
+
+def relu_add_supported(dtype, n):
+    return bool(N.lib().mlpk_relu_add_supported(dtype_code(dtype), n))
+
+
+def relu_add(y, res, out, n):
+    """out = res + relu(y) over n dense elements (mlpk_relu_add); res None: relu(y); out may be y or res"""
+    N.check(N.lib().mlpk_relu_add(dtype_code(y.dtype), ptr(y), ptr(res), ptr(out), n, stream()), "mlpk_relu_add")
+
+
+def relu_maxpool3s2_supported(dtype, B, H, W, C):
+    return bool(N.lib().mlpk_relu_maxpool3s2_nhwc_supported(dtype_code(dtype), B, H, W, C))
+
+
+def relu_maxpool3s2_nhwc(y, out, B, H, W, C):
+    """out (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C) = MaxPool2d(3, 2, 1)(relu(y)) on dense channel-last rows (mlpk_relu_maxpool3s2_nhwc)"""
+    N.check(N.lib().mlpk_relu_maxpool3s2_nhwc(dtype_code(y.dtype), ptr(y), ptr(out), B, H, W, C, stream()), "mlpk_relu_maxpool3s2_nhwc")
+
+
 def dwconv_plain_nhwc(x, out, B, H, W, C, k, w, bias):
     """depthwise Conv2d(k, groups = C, padding = "same") on dense channel-last rows, no epilogue (mlpk_dwconv_plain_nhwc): w fp32 [k * k][C]"""
     N.check(N.lib().mlpk_dwconv_plain_nhwc(dtype_code(x.dtype), 0, ptr(x), ptr(out), B, H, W, C, k, ptr(w), ptr(bias), stream()), "mlpk_dwconv_plain_nhwc")

@@ -20,6 +20,7 @@ from .raft_mlp import RaftMLP  # noqa: F401
 from .active_mlp import ActiveMLP, ActiveSmall, ActiveBase, ActiveLarge  # noqa: F401
 from .dyna_mlp import DynaMixer  # noqa: F401
 from .sequencer import Sequencer2D  # noqa: F401
+from .conv_mlp import ConvMLP, convmlp_s, convmlp_m, convmlp_l  # noqa: F401
 from .utils import Shift  # noqa: F401
 # secondary classes the reference lets users import from the sub-modules
 from .mlp_mixer import MLPMixer  # noqa: F401
@@ -32,4 +33,4 @@ from .cycle_mlp import CycleFC, CycleMLP, CycleBlock  # noqa: F401
 __all__ = ["gMLPForImageClassification", "ResMLPForImageClassification", "MLPMixerForImageClassification", "ViP",
            "S2MLPv1", "S2MLPv1_deep", "S2MLPv1_wide", "S2MLPv2", "ConvMixer", "AS_MLP", "SparseMLP", "HireMLP", "MS_MLP", "SwinMLP", "CycleNet",
            "CycleMLP_B1", "CycleMLP_B2", "CycleMLP_B3", "CycleMLP_B4", "CycleMLP_B5", "WaveMLP", "RaftMLP", "ActiveMLP",
-           "ActiveSmall", "ActiveBase", "ActiveLarge", "DynaMixer", "Sequencer2D", "Shift"]
+           "ActiveSmall", "ActiveBase", "ActiveLarge", "DynaMixer", "Sequencer2D", "ConvMLP", "convmlp_s", "convmlp_m", "convmlp_l", "Shift"]
